@@ -68,6 +68,42 @@ def loss_fns():
             'norm_rgb': M.MaskedMSELoss(16, 1, norm_pix=True)}
 
 
+DUMP_SAMPLE = {'pred': 1 << 20, 'params': 1 << 22}      # elements per sampled array: 4 x 4 MiB of predictions + 16 MiB of parameters
+
+
+def _sample_flat(t: torch.Tensor, n: int, seed: int) -> torch.Tensor:
+    """`t` flattened, or (when larger than n) the n elements at fixed, sorted, seeded positions -- the same positions in every
+    run of the same shape, so that two builds can be compared element for element."""
+    import numpy as np
+    t = t.detach().reshape(-1)
+    if t.numel() <= n:
+        return t
+    idx = np.sort(np.random.default_rng(seed).choice(t.numel(), size=n, replace=False))
+    return t[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(out_dir: str, last: dict, model) -> list:
+    """--dump-outputs: what the timed step handed its caller in the LAST timed step, as float32 / float64 .npy files (< 64 MiB):
+    loss_total and loss_<task> (float64 scalars), mask_<domain> (B x tokens, whole), pred_<task> (the decoder outputs: all of
+    them, or a seeded sample of DUMP_SAMPLE['pred'] elements) and params (the trainable parameters after the optimiser step,
+    named_parameters() order, flattened and concatenated: a seeded sample of DUMP_SAMPLE['params'] elements)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss_total': last['loss'].detach().double()}
+    arrays.update({f'loss_{k}': v.detach().double() for k, v in sorted(last['losses'].items())})
+    arrays.update({f'mask_{k}': v.detach().float() for k, v in sorted(last['masks'].items())})
+    for i, (k, v) in enumerate(sorted(last['preds'].items())):
+        arrays[f'pred_{k}'] = _sample_flat(v, DUMP_SAMPLE['pred'], seed=1000 + i).float()
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters() if p.requires_grad])
+    arrays['params'] = _sample_flat(flat, DUMP_SAMPLE['params'], seed=2000)
+    del flat
+    names = []
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
+        names.append(name)
+    return names
+
+
 def pmc_traffic(dom):
     """HBM bytes per bf16-GEMM launch (average over the launches of one step) from the committed rocprofv3 PMC passes of this
     same command (tools/pmc_traffic.py -> profiles/*_pmc_traffic.json; FETCH_SIZE x2 gfx950 correction + WRITE_SIZE).
@@ -398,7 +434,10 @@ def main():
     ap.add_argument('--enc-bwd-side-cus', type=int, default=0, help='experiment: compute units the encoder backward leaves to its weight-gradient stream (engine.set_enc_bwd_side_cus)')
     ap.add_argument('--dropin-ddp', type=int, default=0, help="1: time the REFERENCE'S loop body against the drop-in boundary instead of the native loop (VERDICT r3 item 7): the model wrapped in torch DistributedDataParallel (world 1, nccl, find_unused_parameters=True, run_pretraining_multimae.py:380-387), forward + losses inside torch.cuda.amp.autocast(), the NativeScaler sequence (GradScaler.scale(loss).backward(), unscale_, gradient norm, GradScaler.step(FusedAdamW), update()); gradients travel through autograd / DDP's reducer (engine.set_direct_grads(False))")
     ap.add_argument('--dry-run', type=int, default=0, help='1: CPU tensors and a type-checking stub of the C ABI (tests/dryrun_harness.py): exercises the LAUNCH path of this script (self-launch, process group, reducer, the JSON line) without a GPU -- the numbers are meaningless and the line says so')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last timed step computed (losses, masks, seeded samples of the predictions and updated parameters) as DIR/<name>.npy, float32 / float64 (bench.dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args.gpus))
     if args.precision is None:
@@ -411,7 +450,7 @@ def main():
         import copy
         import gc
         a2 = copy.copy(args)
-        a2.config, a2.precision, a2.steps, a2.warmup, a2.no_cpu_baseline = 'cfg5', 'mxfp8', 5, 2, True
+        a2.config, a2.precision, a2.steps, a2.warmup, a2.no_cpu_baseline, a2.dump_outputs = 'cfg5', 'mxfp8', 5, 2, True, None
         gc.collect()
         torch.cuda.empty_cache()
         try:
@@ -424,7 +463,7 @@ def main():
         # adapter forms, so that the driver's line shows what the default's storage format buys -- and BASELINE configs[1] (RGB only)
         for key, mods in (('secondary_x3_adapter', dict(fp32_adapter_gemm='x3')), ('secondary_cfg2', dict(config='cfg2'))):
             a3 = copy.copy(args)
-            a3.steps, a3.warmup, a3.no_cpu_baseline, a3.no_kernel_timing = 10, 3, True, True
+            a3.steps, a3.warmup, a3.no_cpu_baseline, a3.no_kernel_timing, a3.dump_outputs = 10, 3, True, True, None
             for k, v in mods.items():
                 setattr(a3, k, v)
             gc.collect()
@@ -527,6 +566,7 @@ def run_once(args):
     fns = loss_fns()
     fp32_adapters = ['semseg'] if 'semseg' in doms else []
     last = {}
+    keep_outputs = bool(getattr(args, 'dump_outputs', None)) and rank == 0      # --dump-outputs: hold the last step's outputs
 
     net, scaler = model, None
     if args.dropin_ddp:
@@ -552,6 +592,8 @@ def run_once(args):
         scaler.step(opt)
         scaler.update()
         last['loss'] = loss
+        if keep_outputs:
+            last.update(preds=preds, masks=masks, losses=losses)
 
     def step():
         if args.dropin_ddp:
@@ -569,6 +611,8 @@ def run_once(args):
             reducer.finish()
         opt.step(loss)                          # isfinite(loss) guard + grad-norm + AdamW: one call, every decision on the device
         last['loss'] = loss
+        if keep_outputs:
+            last.update(preds=preds, masks=masks, losses=losses)
 
     def sync():
         if use_dist:
@@ -628,6 +672,11 @@ def run_once(args):
                    'backward_ms_on_reduced_width_grids': bt['backward_ms_on_reduced_width_grids'],
                    'reading': 'a bucket whose launch_to_done_ms approaches the reduced-width stretch is what finish() waits for; exposed_allreduce_ms_per_step '
                               'is that wait; algbw_gb_s is per bucket under the load of the concurrent backward (8 GPUs, 7 xGMI links x ~153 GB/s: ring bound ~2 x 64 MiB x 7/8 / 153 GB/s = 0.77 ms per bucket unloaded)'}
+    if keep_outputs:
+        names = dump_outputs(args.dump_outputs, last, model)
+        for k in ('preds', 'masks', 'losses'):
+            del last[k]
+        log(f'last timed step written to {args.dump_outputs}: {len(names)} arrays')
     if args.dropin_ddp:
         args.no_kernel_timing = True
     final_loss = float(last['loss'].detach())

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(extra, env_extra=None, timeout=600):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(env_extra or {})
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run', '1', '--steps', '2', '--warmup', '1'] + extra
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run', '1', '--steps', '2', '--warmup', '1'] + extra      # a later --steps wins
     return subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
 
 
@@ -46,3 +46,30 @@ def test_bench_single_rank_dry_run_line_keeps_the_contract():
 def test_bench_refuses_a_launcher_environment_that_disagrees_with_gpus():
     r = _run(['--gpus', '2'], env_extra=dict(WORLD_SIZE='1', RANK='0', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1', MASTER_PORT='29541'), timeout=300)
     assert r.returncode != 0 and 'must agree' in r.stderr
+
+
+def test_bench_dump_outputs_writes_the_last_step_as_float_arrays(tmp_path):
+    """--dump-outputs DIR: the last timed step's losses, masks, predictions and updated parameters as float32 / float64 .npy
+    files, 64 MiB at most in all; the line's `steps` / `ms_per_step` are those of the timed loop."""
+    import numpy as np
+    out_dir = tmp_path / 'dump'
+    r = _run(['--gpus', '1', '--steps', '3', '--dump-outputs', str(out_dir)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
+    assert out['steps'] == 3 and out['ms_per_step'] > 0
+    names = sorted(p.name for p in out_dir.iterdir())
+    doms, tasks = ['depth', 'rgb', 'semseg'], ['depth', 'norm_rgb', 'rgb', 'semseg']
+    assert names == sorted(['loss_total.npy', 'params.npy'] + [f'loss_{t}.npy' for t in tasks] + [f'mask_{d}.npy' for d in doms]
+                           + [f'pred_{t}.npy' for t in tasks]), names
+    total = 0
+    for n in names:
+        a = np.load(out_dir / n)
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        total += a.nbytes
+    assert np.load(out_dir / 'mask_rgb.npy').shape == (2, 196)
+    assert total <= 64 << 20, total
+
+
+def test_bench_refuses_zero_steps():
+    r = _run(['--gpus', '1', '--steps', '0'], timeout=300)
+    assert r.returncode != 0 and '--steps' in r.stderr
