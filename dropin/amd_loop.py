@@ -102,3 +102,19 @@ class LossScaler:
 
     def load_state_dict(self, state_dict):
         pass
+
+
+def staged_loader(data_loader, args, device=None):
+    """Wraps the pre-training DataLoader (run_pretraining_multimae.py:472) in ``multimae_amd.StagedLoader``: it yields
+    ``(x_on_device, target)`` with every batch copied on the stager's stream one step ahead, compact arrays
+    (``dropin.amd_data.CompactAugmentation``) decoded on the device, and the depth standardised there when
+    ``args.standardize_depth`` -- then pass ``standardize_depth=False`` to ``train_one_epoch``.  The loop's
+    ``tensor.to(device, non_blocking=True)`` (:482-485) becomes a no-op."""
+    from multimae_amd import staging
+    default = getattr(args, 'imagenet_default_mean_and_std', True)
+    mean = staging.IMAGENET_DEFAULT_MEAN if default else staging.IMAGENET_INCEPTION_MEAN
+    std = staging.IMAGENET_DEFAULT_STD if default else staging.IMAGENET_INCEPTION_STD
+    device = torch.device(device if device is not None else getattr(args, 'device', 'cuda'))
+    stager = staging.BatchStager(device, mean, std,
+                                 standardize_depth=(0.1, 0.9, 1e-6) if getattr(args, 'standardize_depth', False) else None)
+    return staging.StagedLoader(data_loader, stager)

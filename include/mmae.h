@@ -833,6 +833,23 @@ int mmae_opt_step(const mmae_opt_desc* d, void* stream);
  * ------------------------------------------------------------------------- */
 int mmae_depth_standardize(const float* x, float* y, int B, int n, int lo, int hi, float eps, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * On-device ingest of a host-decoded batch (multimae_amd/staging.py): the conversions utils/datasets.py:93-107
+ * (DataAugmentationForMultiMAE) makes on the host, applied after the H2D copy of the compact arrays the decoder produced, so
+ * 65 MB cross PCIe per cfg3 batch of 256 instead of 212 MB.  Every result is bit-identical to the host conversion.
+ *   rgb     x uint8 [B][H][W][3] (HWC) -> y f32 [B][3][H][W]; y = table[c][x], table f32 [3][256] built by the caller with
+ *           torchvision's own ops, (float(u) / 255 - mean[c]) / std[c] (to_tensor + normalize), so the kernel does no division.
+ *   depth   x uint16 (x_dtype MMAE_U16, Pillow 'I;16') or int32 (MMAE_I32, Pillow 'I') [B][n] -> y f32 [B][n] = float(v) * 2^-16,
+ *           which rounds as torch.Tensor(np.array(img) / 2**16) does.  standardize != 0: y = mmae_depth_standardize of that in
+ *           the same launch (lo, hi, eps as there), bit-identical to converting first.
+ *   semseg  x uint8 [B][n] -> y int64 [B][n] (pil_to_tensor(..).to(torch.long)).
+ * ------------------------------------------------------------------------- */
+#define MMAE_U16 6     /* ingest only: host-decoded depth maps */
+#define MMAE_I32 7
+int mmae_ingest_rgb_u8(const uint8_t* x, const float* table, float* y, int B, int H, int W, void* stream);
+int mmae_ingest_depth(const void* x, int x_dtype, float* y, int B, int n, int standardize, int lo, int hi, float eps, void* stream);
+int mmae_ingest_semseg_u8(const uint8_t* x, int64_t* y, int B, int n, void* stream);
+
 /* hardware probes used by tests/ to pin instruction semantics the kernels rely on */
 /* SemSegInputAdapter(interpolate_class_emb=True) (input_adapters.py:192-198): the class-embedding image resized by 1 / patch with
  * nn.Upsample(bilinear) -- per token the mean of the centre taps -- as out f32 [B][E][H/ph][W/pw] (then projected like a 1 x 1 patch

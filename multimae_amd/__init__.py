@@ -3,7 +3,7 @@
 Public surface = the reference's ``multimae`` package surface for that path
 (multimae/__init__.py): criterion, input adapters, MultiMAE / MultiViT + factories,
 SpatialOutputAdapter; plus the engine controls (precision, parameter arena, fused optimiser,
-data-parallel gradient reducer).
+data-parallel gradient reducer) and the batch stager (host batches copied on their own stream, decoded on the device).
 """
 from . import engine  # noqa: F401
 from .data_ops import truncated_depth_standardize  # noqa: F401
@@ -13,5 +13,6 @@ from .multimae import (MultiMAE, MultiViT, multivit_base, multivit_large,  # noq
                        pretrain_multimae_base, pretrain_multimae_large)
 from .output_adapters import LinearOutputAdapter, SpatialOutputAdapter  # noqa: F401
 from .registry import create_model, register_model  # noqa: F401
+from .staging import BatchStager, StagedLoader  # noqa: F401
 
 __version__ = '0.1.0'

@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get('MMAE_LIB') or os.path.join(_PKG, 'libmmae_hip.so')   
 F32, BF16, F32X3, F32F16 = 0, 1, 2, 3
 MXFP8 = 4
 F16 = 5            # fp16 storage (the fp32 output adapters' 'h16' mode), see mmae.h
+U16, I32 = 6, 7    # mmae_ingest_depth only: host-decoded depth maps
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_G, EPI_MUL = 0, 1, 2, 3, 4
 
 

@@ -19,6 +19,7 @@ int mmae_check_launch(const char* what);
 int mmae_cu_count();                                          // runtime.hip: compute units of the CURRENT device (cached per device)
 int mmae_cu_side();                                           // experiment: CUs set aside for the side stream's grouped weight gradients (0 = off)
 int mmae_cu_avail();                                          // ... minus the ones mmae_gemm_cu_reserve() keeps free: width of a persistent GEMM grid
+int mmae_depth_standardize_int(const void* x, int x_dtype, float* y, int B, int n, int lo, int hi, float eps, hipStream_t stream);  // depth.hip
 
 // A/B switches of the experiments (environment variables) exist only in builds with -DMMAE_EXPERIMENTS (make EXTRA=-DMMAE_EXPERIMENTS);
 // the production library reads no environment: every switch is its default.

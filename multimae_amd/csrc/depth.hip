@@ -30,23 +30,51 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {    // all
     return t;
 }
 
-__global__ void __launch_bounds__(1024) depth_standardize_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int lo, int hi,
-                                                                 float eps) {
+// Element loaders: the kernel below is one thread-to-element mapping and one fp64 reduction order for every input form, so a
+// map decoded on the device (csrc/ingest.hip) and standardised in the same launch is bit-identical to one converted first and
+// standardised as fp32.  key(i) is an order-preserving integer key of val(i) in the low KEY_BITS bits; val_of(key) inverts it.
+struct LoadF32 {                                                  // the fp32 map as it is
+    static constexpr int KEY_BITS = 32;
+    const float* p;
+    __device__ __forceinline__ LoadF32 at(long long o) const { return {p + o}; }
+    __device__ __forceinline__ float val(int i) const { return p[i]; }
+    __device__ __forceinline__ unsigned key(int i) const { return key_of(p[i]); }
+    __device__ __forceinline__ static float val_of_key(unsigned k) { return val_of(k); }
+};
+struct LoadU16 {                                                  // 16-bit PNG depth: v * 2^-16 is exact and strictly increasing in v,
+    static constexpr int KEY_BITS = 16;                           // so the raw value is the key: 2 passes over 2-byte elements
+    const uint16_t* p;
+    __device__ __forceinline__ LoadU16 at(long long o) const { return {p + o}; }
+    __device__ __forceinline__ float val(int i) const { return (float)p[i] * 0x1p-16f; }
+    __device__ __forceinline__ unsigned key(int i) const { return p[i]; }
+    __device__ __forceinline__ static float val_of_key(unsigned k) { return (float)k * 0x1p-16f; }
+};
+struct LoadI32 {                                                  // Pillow 'I' depth (a bicubic resize may leave 0..65535).  The key is the
+    static constexpr int KEY_BITS = 32;                           // one of the CONVERTED value: beyond |v| = 2^24 distinct integers round to
+    const int32_t* p;                                             // one float, and a key of the integer would then count them apart
+    __device__ __forceinline__ LoadI32 at(long long o) const { return {p + o}; }
+    __device__ __forceinline__ float val(int i) const { return (float)p[i] * 0x1p-16f; }
+    __device__ __forceinline__ unsigned key(int i) const { return key_of(val(i)); }
+    __device__ __forceinline__ static float val_of_key(unsigned k) { return val_of(k); }
+};
+
+template <class L>
+__global__ void __launch_bounds__(1024) depth_standardize_kernel(L x, float* __restrict__ y, int n, int lo, int hi, float eps) {
     __shared__ int hist[2][256];
     __shared__ unsigned sel_prefix[2];
     __shared__ int sel_rank[2], sel_less[2], sel_eq[2];
     __shared__ double red[16];
-    const float* xs = x + (long long)blockIdx.x * n;
+    const L xs = x.at((long long)blockIdx.x * n);
     float* ys = y + (long long)blockIdx.x * n;
     const int tid = threadIdx.x;
     if (tid < 2) { sel_prefix[tid] = 0u; sel_rank[tid] = tid == 0 ? lo : hi - 1; sel_less[tid] = 0; }
-    for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int shift = L::KEY_BITS - 8; shift >= 0; shift -= 8) {
         for (int i = tid; i < 512; i += 1024) (&hist[0][0])[i] = 0;
         __syncthreads();
         const unsigned p0 = sel_prefix[0], p1 = sel_prefix[1];
         for (int i = tid; i < n; i += 1024) {
-            const unsigned k = key_of(xs[i]);
-            const unsigned top = shift == 24 ? 0u : (k >> (shift + 8));
+            const unsigned k = xs.key(i);
+            const unsigned top = shift == L::KEY_BITS - 8 ? 0u : (k >> (shift + 8));
             const int bin = (k >> shift) & 255;
             if (top == p0) atomicAdd(&hist[0][bin], 1);
             if (top == p1) atomicAdd(&hist[1][bin], 1);
@@ -63,29 +91,27 @@ __global__ void __launch_bounds__(1024) depth_standardize_kernel(const float* __
         __syncthreads();
     }
     const unsigned k1 = sel_prefix[0], k2 = sel_prefix[1];
-    const float v1 = val_of(k1), v2 = val_of(k2);
+    const float v1 = L::val_of_key(k1), v2 = L::val_of_key(k2);
     // copies of the cut values inside [lo, hi)
     const int cnt = hi - lo;
     const int n1 = (k1 == k2) ? cnt : (sel_less[0] + sel_eq[0] - lo);
     const int n2 = (k1 == k2) ? 0 : (hi - sel_less[1]);
     double s = 0.0;
     for (int i = tid; i < n; i += 1024) {
-        const float f = xs[i];
-        const unsigned k = key_of(f);
-        if (k > k1 && k < k2) s += (double)f;
+        const unsigned k = xs.key(i);
+        if (k > k1 && k < k2) s += (double)xs.val(i);
     }
     s = block_sum_d(s, red) + (double)n1 * (double)v1 + (double)n2 * (double)v2;
     const double mean = s / (double)cnt;
     double q = 0.0;
     for (int i = tid; i < n; i += 1024) {
-        const float f = xs[i];
-        const unsigned k = key_of(f);
-        if (k > k1 && k < k2) { const double d = (double)f - mean; q += d * d; }
+        const unsigned k = xs.key(i);
+        if (k > k1 && k < k2) { const double d = (double)xs.val(i) - mean; q += d * d; }
     }
     q = block_sum_d(q, red) + (double)n1 * ((double)v1 - mean) * ((double)v1 - mean) + (double)n2 * ((double)v2 - mean) * ((double)v2 - mean);
     const float var = (float)(q / (double)(cnt - 1));            // unbiased, as Tensor.var
     const float mu = (float)mean, rs = 1.0f / sqrtf(var + eps);
-    for (int i = tid; i < n; i += 1024) ys[i] = (xs[i] - mu) * rs;
+    for (int i = tid; i < n; i += 1024) ys[i] = (xs.val(i) - mu) * rs;
 }
 
 }  // namespace
@@ -93,6 +119,15 @@ __global__ void __launch_bounds__(1024) depth_standardize_kernel(const float* __
 extern "C" int mmae_depth_standardize(const float* x, float* y, int B, int n, int lo, int hi, float eps, void* stream) {
     MMAE_REQUIRE(x && y && B > 0 && n > 1, "depth_standardize: bad argument");
     MMAE_REQUIRE(lo >= 0 && hi <= n && hi - lo >= 2, "depth_standardize: need 0 <= lo, lo + 2 <= hi <= n");
-    hipLaunchKernelGGL(depth_standardize_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, y, n, lo, hi, eps);
+    hipLaunchKernelGGL(depth_standardize_kernel<LoadF32>, dim3(B), dim3(1024), 0, (hipStream_t)stream, LoadF32{x}, y, n, lo, hi, eps);
     return mmae_check_launch("depth_standardize");
+}
+
+// mmae_ingest_depth's fused form (csrc/ingest.hip): the same kernel over the host-decoded integer map; arguments checked there
+int mmae_depth_standardize_int(const void* x, int x_dtype, float* y, int B, int n, int lo, int hi, float eps, hipStream_t stream) {
+    if (x_dtype == MMAE_U16)
+        hipLaunchKernelGGL(depth_standardize_kernel<LoadU16>, dim3(B), dim3(1024), 0, stream, LoadU16{(const uint16_t*)x}, y, n, lo, hi, eps);
+    else
+        hipLaunchKernelGGL(depth_standardize_kernel<LoadI32>, dim3(B), dim3(1024), 0, stream, LoadI32{(const int32_t*)x}, y, n, lo, hi, eps);
+    return mmae_check_launch("ingest_depth");
 }

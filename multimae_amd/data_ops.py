@@ -24,3 +24,81 @@ def truncated_depth_standardize(depth: torch.Tensor, lo: float = 0.1, hi: float 
     _lib.check(_lib.load().mmae_depth_standardize(x.data_ptr(), y.data_ptr(), B, n, int(lo * n), int(hi * n), eps, ops._stream()),
                'depth_standardize')
     return y.view(depth.shape)
+
+
+# --------------------------------------------------------------------------- on-device ingest (csrc/ingest.hip) --
+# The to-tensor conversions of utils/datasets.py:93-107 applied after the H2D copy of the compact arrays the decoder produced.
+# multimae_amd.staging.BatchStager queues them on its copy stream; each is bit-identical to the host conversion it replaces.
+
+def rgb_table(mean, std) -> torch.Tensor:
+    """CPU f32 [3, 256]: the value of every uint8 in every channel, by torchvision's own ops -- ``to_tensor`` (``.float().div(255)``)
+    then ``normalize`` (``.sub(mean).div(std)``, mean / std as f32 tensors)."""
+    u = torch.arange(256, dtype=torch.uint8).float().div(255)
+    m = torch.as_tensor(mean, dtype=torch.float32).view(3, 1)
+    s = torch.as_tensor(std, dtype=torch.float32).view(3, 1)
+    return u.view(1, 256).sub(m).div(s).contiguous()
+
+
+def ingest_rgb_u8(x: torch.Tensor, table: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """(B, H, W, 3) uint8 HWC -> (B, 3, H, W) f32: ``out[b, c, h, w] = table[c, x[b, h, w, c]]`` (``table`` from ``rgb_table``, on the device)."""
+    ops._require_gpu(x, 'rgb')
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f'ingest_rgb_u8: expected (B, H, W, 3) uint8, got {tuple(x.shape)} {x.dtype}')
+    if table.dtype != torch.float32 or table.shape != (3, 256) or not table.is_contiguous() or table.device != x.device:
+        raise ValueError('ingest_rgb_u8: table must be a contiguous f32 (3, 256) tensor on the input\'s device')
+    B, H, W, _ = x.shape
+    x = x.contiguous()
+    out = _out(out, (B, 3, H, W), torch.float32, x.device, 'ingest_rgb_u8')
+    _lib.check(_lib.load().mmae_ingest_rgb_u8(x.data_ptr(), table.data_ptr(), out.data_ptr(), B, H, W, ops._stream()), 'ingest_rgb_u8')
+    return out
+
+
+def ingest_depth(x: torch.Tensor, standardize=None, out: torch.Tensor = None) -> torch.Tensor:
+    """(B, H, W) or (B, 1, H, W) uint16 / int32 -> (B, 1, H, W) f32 ``float(v) * 2**-16`` (``torch.Tensor(np.array(img) / 2**16)``).
+    ``standardize=(lo, hi, eps)`` also applies ``truncated_depth_standardize(.., lo, hi, eps)`` in the same launch, bit-identical to
+    converting first."""
+    ops._require_gpu(x, 'depth')
+    codes = {torch.uint16: _lib.U16, torch.int32: _lib.I32}
+    if x.dtype not in codes or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[1] != 1):
+        raise ValueError(f'ingest_depth: expected (B, H, W) uint16 / int32, got {tuple(x.shape)} {x.dtype}')
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    n = H * W
+    x = x.contiguous()
+    out = _out(out, (B, 1, H, W), torch.float32, x.device, 'ingest_depth')
+    lo, hi, eps = standardize if standardize is not None else (0.0, 0.0, 0.0)
+    _lib.check(_lib.load().mmae_ingest_depth(x.data_ptr(), codes[x.dtype], out.data_ptr(), B, n, int(standardize is not None),
+                                             int(lo * n), int(hi * n), eps, ops._stream()), 'ingest_depth')
+    return out
+
+
+def ingest_semseg_u8(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """(B, h, w) uint8 -> int64 (``pil_to_tensor(..).to(torch.long)``); every id passes through unchanged."""
+    ops._require_gpu(x, 'semseg')
+    if x.dtype != torch.uint8 or x.dim() != 3:
+        raise ValueError(f'ingest_semseg_u8: expected (B, h, w) uint8, got {tuple(x.shape)} {x.dtype}')
+    B = x.shape[0]
+    x = x.contiguous()
+    out = _out(out, tuple(x.shape), torch.int64, x.device, 'ingest_semseg_u8')
+    _lib.check(_lib.load().mmae_ingest_semseg_u8(x.data_ptr(), out.data_ptr(), B, x.numel() // max(B, 1), ops._stream()), 'ingest_semseg_u8')
+    return out
+
+
+def depth_standardize_(x: torch.Tensor, lo: float = 0.1, hi: float = 0.9, eps: float = 1e-6) -> torch.Tensor:
+    """``truncated_depth_standardize`` in place, on a contiguous f32 (B, ...) map (the kernel allows y to alias x)."""
+    ops._require_gpu(x, 'depth')
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('depth_standardize_: expected a contiguous f32 tensor')
+    B = x.shape[0]
+    n = x.numel() // B
+    _lib.check(_lib.load().mmae_depth_standardize(x.data_ptr(), x.data_ptr(), B, n, int(lo * n), int(hi * n), eps, ops._stream()),
+               'depth_standardize')
+    return x
+
+
+def _out(out, shape, dtype, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError(f'{what}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, '
+                         f'got {tuple(out.shape)} {out.dtype} on {out.device}')
+    return out

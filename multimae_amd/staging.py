@@ -1,0 +1,270 @@
+"""Batch staging: host batches copied on a dedicated stream and decoded on the device, one batch ahead of the step.
+
+The reference loop moves each batch with ``tensor.to(device, non_blocking=True)`` on the compute stream
+(run_pretraining_multimae.py:482-485), so the H2D copy of the 212 MB fp32 / int64 cfg3 batch (B = 256) runs in series with the
+step.  ``BatchStager`` queues the copy on a stream of its own and, for the compact form the decoder produced before ``to_tensor``
+(uint8 HWC rgb, uint16 / int32 depth, uint8 semseg: 65 MB), the conversions after it (csrc/ingest.hip), then records a ready
+event; ``StagedLoader`` stages batch k + 1 before it hands out batch k, so that copy runs under step k.
+
+Forms accepted per task (anything else raises ``ValueError``):
+
+  task                  compact form (decoded on the device)       reference form (copied as it is)
+  rgb                   uint8 (B, H, W, 3)                         float32 (B, 3, H, W)
+  depth                 uint16 / int32 (B, H, W) or (B, 1, H, W)   float32 (B, 1, H, W)
+  semseg, semseg_coco   uint8 (B, h, w)                            int64 (B, h, w)
+
+Depth comes out as (B, 1, H, W) f32, standardised on the copy stream when ``standardize_depth=(lo, hi, eps)`` (in the decode
+launch for the compact form); the training loop must then not standardise it again.
+"""
+from __future__ import annotations
+
+import collections
+from typing import Dict, Optional
+
+import torch
+
+from . import data_ops
+
+IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+IMAGENET_INCEPTION_MEAN, IMAGENET_INCEPTION_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
+
+_COMPACT = {'rgb': 'uint8 (B, H, W, 3)', 'depth': 'uint16 / int32 (B, H, W) or (B, 1, H, W)', 'semseg': 'uint8 (B, h, w)'}
+_REFERENCE = {'rgb': 'float32 (B, 3, H, W)', 'depth': 'float32 (B, 1, H, W)', 'semseg': 'int64 (B, h, w)'}
+
+
+def _kind(task: str) -> Optional[str]:
+    return 'semseg' if task in ('semseg', 'semseg_coco') else task if task in ('rgb', 'depth') else None
+
+
+def batch_form(task: str, t) -> str:
+    """'compact' or 'reference' for one task's batch tensor; ``ValueError`` naming the task, shape and dtype otherwise."""
+    k, s, d = _kind(task), tuple(t.shape), t.dtype
+    compact = reference = False
+    if k == 'rgb':
+        compact = d == torch.uint8 and len(s) == 4 and s[3] == 3
+        reference = d == torch.float32 and len(s) == 4 and s[1] == 3
+    elif k == 'depth':
+        compact = d in (torch.uint16, torch.int32) and (len(s) == 3 or (len(s) == 4 and s[1] == 1))
+        reference = d == torch.float32 and len(s) == 4 and s[1] == 1
+    elif k == 'semseg':
+        compact = d == torch.uint8 and len(s) == 3
+        reference = d == torch.int64 and len(s) == 3
+    if k is not None and (compact or reference) and s[0] > 0 and all(v > 0 for v in s):
+        return 'compact' if compact else 'reference'
+    if k is None:
+        raise ValueError(f'BatchStager: task {task!r} (shape {s}, dtype {d}) is not one of rgb, depth, semseg, semseg_coco')
+    raise ValueError(f'BatchStager: task {task!r}: shape {s}, dtype {d} is neither the compact form ({_COMPACT[k]}) '
+                     f'nor the reference form ({_REFERENCE[k]}), or is empty')
+
+
+def batch_forms(batch: Dict[str, torch.Tensor]) -> Dict[str, str]:
+    """``batch_form`` of every task, plus one batch size across the tasks."""
+    if not isinstance(batch, dict) or not batch:
+        raise ValueError(f'BatchStager: a batch is a non-empty dict task -> tensor, got {type(batch).__name__}')
+    forms = {task: batch_form(task, t) for task, t in batch.items()}
+    sizes = {task: int(t.shape[0]) for task, t in batch.items()}
+    if len(set(sizes.values())) != 1:
+        raise ValueError(f'BatchStager: the tasks disagree on the batch size: {sizes}')
+    return forms
+
+
+def _out_spec(task: str, t, form: str):
+    """(shape, dtype) of the staged tensor"""
+    if form == 'reference':
+        return tuple(t.shape), t.dtype
+    k = _kind(task)
+    if k == 'rgb':
+        B, H, W, _ = t.shape
+        return (B, 3, H, W), torch.float32
+    if k == 'depth':
+        return (t.shape[0], 1, t.shape[-2], t.shape[-1]), torch.float32
+    return tuple(t.shape), torch.int64
+
+
+def _nbytes(shape, dtype) -> int:
+    n = 1
+    for v in shape:
+        n *= int(v)
+    return n * torch.empty((), dtype=dtype).element_size()
+
+
+def bytes_per_batch(batch, standardize_depth: bool = False) -> Dict[str, int]:
+    """Bytes one batch costs: ``h2d`` copied over PCIe, ``device`` in the staged tensors, ``hbm`` the decode / standardisation
+    kernels read and write once (the selection passes of the standardisation re-read the map from L2, not counted).  ``batch``
+    may hold meta tensors: only shapes and dtypes are read."""
+    forms = batch_forms(batch)
+    h2d = dev = hbm = 0
+    for task, t in batch.items():
+        inp = _nbytes(t.shape, t.dtype)
+        out = _nbytes(*_out_spec(task, t, forms[task]))
+        h2d += inp
+        dev += out
+        if forms[task] == 'compact':
+            hbm += inp + out
+        elif standardize_depth and _kind(task) == 'depth':
+            hbm += 2 * out
+    return {'h2d': h2d, 'device': dev, 'hbm': hbm}
+
+
+class StagedBatch:
+    """A batch queued on the stager's copy stream: ``tensors`` become valid for a stream once it has waited on ``event``
+    (``BatchStager.get`` does both)."""
+    __slots__ = ('tensors', 'event', 'owned')
+
+    def __init__(self, tensors, event, owned):
+        self.tensors, self.event, self.owned = tensors, event, owned
+
+
+class BatchStager:
+    """Copies host batches to ``device`` on one dedicated stream and decodes compact forms there (module docstring).
+
+    Host side: pinned tensors (DataLoader ``pin_memory=True``) are copied from directly; pageable ones are first copied into one
+    of two pinned slots the stager owns, and a slot is rewritten only after the event of its previous H2D has completed.  Every
+    host tensor is referenced until its copy's event has completed.  Outputs come from torch's caching allocator (allocated on
+    the copy stream, ``record_stream``-ed to the consumer by ``get``), so callers may keep them."""
+
+    def __init__(self, device=None, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, standardize_depth=None):
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError(f'BatchStager: device {self.device} is not a GPU (the decode runs on HIP kernels only)')
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        if standardize_depth is not None:
+            lo, hi, eps = standardize_depth
+            standardize_depth = (float(lo), float(hi), float(eps))
+        self.standardize_depth = standardize_depth
+        self.stream = torch.cuda.Stream(self.device)
+        with torch.cuda.stream(self.stream):
+            self.table = data_ops.rgb_table(mean, std).to(self.device)
+        self.stream.synchronize()
+        self._slots = [{}, {}]                     # task -> pinned uint8 buffer
+        self._slot_event = [None, None]
+        self._next_slot = 0
+        self._held = collections.deque()           # (event, host tensors) until the event has completed
+
+    def bytes_per_batch(self, batch) -> Dict[str, int]:
+        return bytes_per_batch(batch, self.standardize_depth is not None)
+
+    def _release(self):
+        while self._held and self._held[0][0].query():
+            self._held.popleft()
+
+    def _pinned(self, slot: int, task: str, t: torch.Tensor) -> torch.Tensor:
+        n = t.numel() * t.element_size()
+        buf = self._slots[slot].get(task)
+        if buf is None or buf.numel() < n:
+            buf = self._slots[slot][task] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+        dst = buf[:n].view(t.dtype).view(t.shape)
+        dst.copy_(t)
+        return dst
+
+    def stage(self, batch: Dict[str, torch.Tensor], into: Optional[Dict[str, torch.Tensor]] = None,
+              after: Optional[torch.cuda.Event] = None) -> StagedBatch:
+        """Queue one batch.  ``into``: caller-owned static tensors (e.g. the inputs a ``graph.StepGraph`` replays on) to write
+        instead of new ones; the copy stream first waits on ``after``, an event the caller recorded after its last use of them."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('BatchStager.stage: not allowed inside a graph capture (stage between replays, with into=)')
+        forms = batch_forms(batch)
+        for task, t in batch.items():
+            if t.is_cuda:
+                raise ValueError(f'BatchStager: task {task!r} is already on {t.device}; the stager copies host batches')
+        if into is not None:
+            for task, t in batch.items():
+                shape, dtype = _out_spec(task, t, forms[task])
+                o = into.get(task)
+                if o is None or tuple(o.shape) != shape or o.dtype != dtype or o.device != self.device or not o.is_contiguous():
+                    raise ValueError(f'BatchStager: into[{task!r}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}')
+        self._release()
+        host = {task: t.contiguous() for task, t in batch.items()}
+        pageable = [task for task, t in host.items() if not t.is_pinned()]
+        slot = None
+        if pageable:
+            slot, self._next_slot = self._next_slot, self._next_slot ^ 1
+            if self._slot_event[slot] is not None:
+                self._slot_event[slot].synchronize()          # the slot's previous H2D has completed
+            for task in pageable:
+                host[task] = self._pinned(slot, task, host[task])
+        out = {}
+        with torch.cuda.stream(self.stream):
+            if after is not None:
+                self.stream.wait_event(after)
+            for task, h in host.items():
+                o = None if into is None else into[task]
+                out[task] = self._stage_one(task, h, forms[task], o)
+            event = torch.cuda.Event()
+            event.record(self.stream)
+        if slot is not None:
+            self._slot_event[slot] = event
+        self._held.append((event, list(batch.values()) + list(host.values())))
+        return StagedBatch(out, event, into is None)
+
+    def _stage_one(self, task, h, form, o):
+        kind = _kind(task)
+        if form == 'reference':
+            d = torch.empty(h.shape, dtype=h.dtype, device=self.device) if o is None else o
+            d.copy_(h, non_blocking=True)
+            if kind == 'depth' and self.standardize_depth is not None:
+                data_ops.depth_standardize_(d, *self.standardize_depth)
+            return d
+        src = h.view(torch.int16) if h.dtype == torch.uint16 else h     # the copy moves bytes; uint16 has few kernels of its own in torch
+        d = torch.empty(src.shape, dtype=src.dtype, device=self.device)
+        d.copy_(src, non_blocking=True)
+        if kind == 'rgb':
+            return data_ops.ingest_rgb_u8(d, self.table, out=o)
+        if kind == 'depth':
+            d = d.view(h.dtype)
+            return data_ops.ingest_depth(d, standardize=self.standardize_depth, out=o)
+        return data_ops.ingest_semseg_u8(d, out=o)
+
+    def get(self, staged: StagedBatch) -> Dict[str, torch.Tensor]:
+        """The staged tensors, made safe to use on the current stream: it waits on the ready event, and each tensor the stager
+        allocated is ``record_stream``-ed to it."""
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(staged.event)
+        if staged.owned:
+            for t in staged.tensors.values():
+                t.record_stream(cur)
+        return dict(staged.tensors)
+
+    def __call__(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """stage + get: the copy still runs on the copy stream, but nothing overlaps it (StagedLoader prefetches)."""
+        return self.get(self.stage(batch))
+
+
+class StagedLoader:
+    """Iterates ``iterable`` with prefetch depth 1: batch k + 1 is staged before batch k is handed out, so its copy runs under
+    step k (also with a ``torch.cuda.synchronize()`` at the end of every step).  Items are a batch dict or a tuple / list whose
+    first element is one (a DataLoader's ``(x, target)``); the rest passes through."""
+
+    def __init__(self, iterable, stager: BatchStager):
+        self.iterable, self.stager = iterable, stager
+
+    def __len__(self):
+        return len(self.iterable)
+
+    def _stage(self, item):
+        if isinstance(item, dict):
+            return self.stager.stage(item), None
+        if isinstance(item, (tuple, list)) and item and isinstance(item[0], dict):
+            return self.stager.stage(item[0]), (type(item), item[1:])
+        raise ValueError(f'StagedLoader: an item is a batch dict or a tuple (batch dict, ...), got {type(item).__name__}')
+
+    def _get(self, staged):
+        sb, rest = staged
+        x = self.stager.get(sb)
+        if rest is None:
+            return x
+        cls, tail = rest
+        return (x, *tail) if cls is tuple else cls([x, *tail])
+
+    def __iter__(self):
+        it = iter(self.iterable)
+        try:
+            cur = self._stage(next(it))
+        except StopIteration:
+            return
+        for item in it:
+            nxt = self._stage(item)
+            yield self._get(cur)
+            cur = nxt
+        yield self._get(cur)
