@@ -12,7 +12,13 @@ AdamW(betas .9/.95, wd .05 on every tensor).  Synthetic inputs resident in HBM, 
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 5
     python bench.py --gpus 8 --steps 20 --warmup 5        # no launcher in the environment: re-executes itself under the line above
 
-Prints ONE JSON line (rank 0) with the driver's contract plus "roofline" and "cpu_baseline".
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run only sets up, warms up, times the steps and (with
+--dump-outputs) writes the last step's outputs; "roofline" and "cpu_baseline" are null in its line.  With --full the same
+command also runs what takes runs of its own, after the timed steps: the per-kernel GEMM timing pass and the encoder step
+("roofline"), the CPU baseline ("cpu_baseline") and, for the default single-GPU cfg3 line, the cfg5 MX-fp8, x3-adapter and
+cfg2 lines beside it ("secondary", "secondary_x3_adapter", "secondary_cfg2").
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 import argparse
 import json
@@ -411,12 +417,15 @@ def main():
     ap.add_argument('--precision', default=None, choices=['bf16', 'fp32', 'mxfp8'],
                     help="'mxfp8': encoder forward / dX / weight-gradient products on OCP MX-fp8 operands (block-scaled MFMA), everything else as bf16.  "
                          "Default: bf16; mxfp8 for --config cfg5 (BASELINE.json configs[4] names the fp8 MFMA path)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the measurements that take runs of their own: the per-kernel GEMM timing pass and the '
+                         'encoder step (roofline), the CPU baseline and the secondary lines.  Off: the line carries the timed steps alone')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-sample-batch', type=int, default=16)
     ap.add_argument('--cpu-threads', type=int, default=0, help='0: best of an 8/16/32/64 sweep')
     ap.add_argument('--cpu-steps', type=int, default=5)
     ap.add_argument('--total-steps', type=int, default=1000, help='length of the cosine lr / wd tables the loop walks (run_pretraining_multimae.py:474-480)')
-    ap.add_argument('--no-kernel-timing', action='store_true')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: skip the per-kernel GEMM timing pass (roofline)')
     ap.add_argument('--adapter-streams', type=int, default=1, help='1: output adapters on separate HIP streams')
     ap.add_argument('--wgrad-stream', type=int, default=1, help='1: weight-gradient GEMMs on a side stream')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for --gpus > 1 ('nccl' = RCCL; 'gloo' for functional tests)")
@@ -427,7 +436,7 @@ def main():
     ap.add_argument('--bf16-buckets', type=int, default=0, help='1: gradient buckets travel as bf16 (half the xGMI bytes, bf16-rounded sum; multimae_amd/dist.py)')
     ap.add_argument('--share-device', type=int, default=0, help='1: every rank uses cuda:0 (functional test of the multi-process path on one GPU; use with --backend gloo)')
     ap.add_argument('--graph', type=int, default=-1, help='1: capture the step once as a hipGraph and replay it (multimae_amd.graph.StepGraph; 1 GPU only). Default 0: on ROCm 7.2 the replay of this ~1 100-node, 10-stream graph measured 46.2 ms/step against 44.1 ms eager')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary line (cfg5 = BASELINE configs[4] geometry, ViT-L, MX-fp8 encoder products, B = 128, a few steps) that the default single-GPU cfg3 run appends as `secondary`')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary lines (cfg5 = BASELINE configs[4] geometry, ViT-L, MX-fp8 encoder products, B = 128, a few steps; the x3 adapter; cfg2) that a --full single-GPU cfg3 run appends as `secondary`, `secondary_x3_adapter`, `secondary_cfg2`')
     ap.add_argument('--gemm-cu-reserve', type=int, default=-1, help='compute units the persistent GEMM grids leave free (for RCCL\'s channel kernels while gradient buckets are in flight); -1: 16 when gradient buckets are exchanged (N > 1 or --force-dist), else 0')
     ap.add_argument('--fp32-adapter-gemm', default='h16', choices=['h16', 'f16', 'x3', 'exact'], help="the fp32 output adapter (semseg) in the bf16 speed mode: 'h16' fp16 storage of its activations / gradients (bf16-pipeline kernels, TF32's significand; default), 'f16' f32 tensors with fp16 operands (one MFMA), 'x3' split bf16 (three), 'exact' f32 MFMA (multimae_amd.engine.set_fp32_adapter_gemm)")
     ap.add_argument('--adapter-cu-share', type=int, default=0, help='experiment: compute units the output adapters\' persistent GEMM grids leave free while they run on separate streams (engine.set_adapter_cu_share)')
@@ -442,10 +451,13 @@ def main():
         sys.exit(self_launch(args.gpus))
     if args.precision is None:
         args.precision = 'mxfp8' if args.config == 'cfg5' else 'bf16'
+    if not args.full:
+        # a plain run: nothing beyond what the headline figure needs
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_secondary = True
     out = run_once(args)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if out is not None and world == 1 and not args.force_dist and args.config == 'cfg3' and not args.no_secondary and not args.batch:
-        # the fp8 configuration of BASELINE.json (configs[4]) measured by the same command, so that the driver's run records it:
+        # --full: the fp8 configuration of BASELINE.json (configs[4]) measured by the same command, so that the full run records it:
         # a short run (the primary line above is the metric; this one is reported beside it, never as `value`)
         import copy
         import gc

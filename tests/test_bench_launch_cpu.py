@@ -70,6 +70,50 @@ def test_bench_dump_outputs_writes_the_last_step_as_float_arrays(tmp_path):
     assert total <= 64 << 20, total
 
 
+def _main_with_recorded_runs(monkeypatch, argv):
+    """bench.main() on `argv` with run_once replaced by a recorder: the arguments of every measured configuration, and the line."""
+    import copy
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    runs = []
+
+    def run_once(a):
+        runs.append(copy.copy(a))
+        return {k: a.config for k in ('metric', 'value', 'unit', 'ms_per_step', 'steps', 'warmup', 'dtype', 'config', 'final_loss', 'roofline')}
+    monkeypatch.setattr(bench, 'run_once', run_once)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+    bench.main()
+    return runs
+
+
+def test_bench_plain_run_measures_the_timed_steps_alone(monkeypatch, capsys):
+    """Without --full: one measured configuration, no kernel timing pass, no CPU baseline, no secondary lines."""
+    runs = _main_with_recorded_runs(monkeypatch, ['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert len(runs) == 1
+    a = runs[0]
+    assert (a.config, a.precision, a.steps, a.warmup) == ('cfg3', 'bf16', 20, 5)
+    assert a.no_kernel_timing and a.no_cpu_baseline and a.no_secondary
+    out = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith('{')][0])
+    assert not any(k.startswith('secondary') for k in out)
+
+
+def test_bench_full_run_keeps_every_extra_measurement(monkeypatch, capsys):
+    """--full: the primary line with the kernel timing pass and the CPU baseline, then the cfg5 MX-fp8, x3-adapter and cfg2 lines."""
+    runs = _main_with_recorded_runs(monkeypatch, ['--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
+    assert [(a.config, a.steps, a.warmup) for a in runs] == [('cfg3', 20, 5), ('cfg5', 5, 2), ('cfg3', 10, 3), ('cfg2', 10, 3)]
+    assert not runs[0].no_kernel_timing and not runs[0].no_cpu_baseline
+    assert runs[1].precision == 'mxfp8' and not runs[1].no_kernel_timing and runs[2].fp32_adapter_gemm == 'x3'
+    out = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith('{')][0])
+    assert out['secondary']['config'] == 'cfg5' and out['secondary_x3_adapter']['config'] == 'cfg3' and out['secondary_cfg2']['config'] == 'cfg2'
+    # the opt-outs keep working under --full
+    runs = _main_with_recorded_runs(monkeypatch, ['--full', '--no-cpu-baseline', '--no-secondary'])
+    assert len(runs) == 1 and runs[0].no_cpu_baseline and not runs[0].no_kernel_timing
+
+
 def test_bench_refuses_zero_steps():
     r = _run(['--gpus', '1', '--steps', '0'], timeout=300)
     assert r.returncode != 0 and '--steps' in r.stderr

@@ -8,6 +8,7 @@ R=$PWD
 V=${1:-baseline}; shift
 S=gpurun_out/r6_${V}_summary.txt
 : > $S
+O=$(dirname "$S")       # the visit's output folder
 EXP=$R/multimae_amd/libmmae_hip_exp.so
 PREV=$R/multimae_amd/libmmae_hip_prev.so
 B="python bench.py --no-cpu-baseline --no-kernel-timing --no-secondary --steps 20 --warmup 5"
@@ -81,9 +82,9 @@ tests)   # the whole GPU suite + smoke
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | cut -c1-220 >> $S
   for f in curve_cfg3_bf16_h16.json adapter_modes_train_cfg3.json mxfp8_trains_cfg5.json dropin_fast_loop.json; do [ -f gpurun_out/$f ] && cp gpurun_out/$f gpurun_out/r6_$f; done
   ;;
-final)   # the round's measurement visit: default line (+ secondaries), other configurations, kernel statistics, PMC traffic, tables, encoder step
-  echo "== bench (default flags)" >> $S
-  timeout 1200 python bench.py > gpurun_out/bench.log 2> gpurun_out/bench.err
+final)   # the round's measurement visit: the --full line (+ secondaries), other configurations, kernel statistics, PMC traffic, tables, encoder step
+  echo "== bench --full" >> $S
+  timeout 1200 python bench.py --full > $O/bench.log 2> $O/bench.err
   grep "timed region\|cpu_baseline\|encoder step" gpurun_out/bench.err | cut -c1-200 >> $S
   grep "^{" gpurun_out/bench.log | tail -1 > gpurun_out/r6_bench_cfg3.json
   cat gpurun_out/r6_bench_cfg3.json >> $S
@@ -96,7 +97,7 @@ final)   # the round's measurement visit: default line (+ secondaries), other co
   run "cfg3 serialized (one stream)" timeout 300 $B --adapter-streams 0 --wgrad-stream 0
   run "cfg2 (RGB only) B=256" timeout 300 $B --config cfg2
   run "cfg5 geometry (ViT-L, bf16) B=128" timeout 600 $B --config cfg5 --precision bf16 --steps 10 --warmup 3
-  timeout 600 python bench.py --no-cpu-baseline --no-secondary --config cfg5 --precision mxfp8 --steps 10 --warmup 3 > gpurun_out/bench_cfg5_mxfp8.log 2> gpurun_out/x.err
+  timeout 600 python bench.py --full --no-cpu-baseline --no-secondary --config cfg5 --precision mxfp8 --steps 10 --warmup 3 > $O/bench_cfg5_mxfp8.log 2> $O/x.err
   grep "^{" gpurun_out/bench_cfg5_mxfp8.log | tail -1 > gpurun_out/r6_bench_cfg5_mxfp8.json
   echo "cfg5 (ViT-L, mxfp8) B=128: $(grep 'timed region' gpurun_out/x.err | sed 's/.*done: //' | cut -c1-120)" >> $S
   timeout 300 python bench.py --no-cpu-baseline --no-kernel-timing --no-secondary --steps 20 --warmup 5 --force-dist 1 > gpurun_out/dist_world1.log 2> gpurun_out/x.err
@@ -136,11 +137,11 @@ envab)   # same-visit A/B of an environment switch of the production path: $1 = 
   ;;
 launch)   # the driver's launch forms on the one GPU a lease has: torchrun at world size 1, and two ranks sharing the device over gloo (all_reduce and rs_ag buckets)
   echo "== torchrun, world size 1 (the driver's N > 1 command line with N = 1)" >> $S
-  ( timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > gpurun_out/launch1.log 2> gpurun_out/launch1.err ); echo "rc=$?" >> $S
+  ( timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/launch1.log 2> $O/launch1.err ); echo "rc=$?" >> $S
   grep "timed region" gpurun_out/launch1.err | cut -c1-160 >> $S; grep "^{" gpurun_out/launch1.log | cut -c1-300 >> $S; grep -i "error\|Traceback" gpurun_out/launch1.err | tail -3 >> $S
   for ex in all_reduce rs_ag; do
     echo "== two ranks on one device, gloo buckets, --dp-exchange $ex (functional test of the N > 1 path with the real kernels)" >> $S
-    ( timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --steps 5 --warmup 2 --backend gloo --share-device 1 --batch 64 --dp-exchange $ex > gpurun_out/launch2.log 2> gpurun_out/launch2.err ); echo "rc=$?" >> $S
+    ( timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 2 --steps 5 --warmup 2 --backend gloo --share-device 1 --batch 64 --dp-exchange $ex > $O/launch2.log 2> $O/launch2.err ); echo "rc=$?" >> $S
     grep "timed region" gpurun_out/launch2.err | cut -c1-160 >> $S; grep "^{" gpurun_out/launch2.log | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print({k: d.get(k) for k in ('value','n_gpus','ms_per_step','rccl_ranks_seen')}, {k: d['data_parallel'].get(k) for k in ('exchange','buckets','backend','exposed_allreduce_ms_per_step')})" >> $S 2>&1; grep -i "error\|Traceback" gpurun_out/launch2.err | tail -3 >> $S
   done
   ;;
