@@ -17,6 +17,9 @@ hooks (13.4 ms), the 345 ``torch.norm`` calls of ``get_grad_norm_`` (9.9 ms), DD
       :391, utils/native_scaler.py:14-62                         2-norm); backward, reducer.finish(), ONE fused library call for
                                                                  norm + clip / skip + non-finite guard + AdamW.  bf16 needs no
                                                                  loss scale: state_dict() reports scale 1.0
+  create_optimizer(args, model_without_ddp, skip_list=..,       create_optimizer_groups(args, model, ...): FusedAdamW(groups=..)
+      get_num_layer=.., get_layer_scale=..)  (fine-tuning,       over the same param groups (no decay for biases / 1-D / skip list,
+      run_finetuning_cls.py:386-389, utils/optim_factory.py:21)  layer-wise lr decay), still one fused library call per step
 
 The patch that wires them in is ``dropin/run_pretraining_multimae.patch`` (three call sites).  Everything else in the script --
 argument parsing, cosine tables, the per-iteration ``param_group['lr']`` assignment (:474-480), ``train_one_epoch`` itself,
@@ -55,22 +58,86 @@ def wrap_model(model: torch.nn.Module, args=None, bucket_mb: float = 64.0):
 def create_optimizer(args, model: torch.nn.Module, reducer=None) -> FusedAdamW:
     """Replaces utils.optim_factory.create_optimizer(args, {'model': model, 'balancer': balancer}) for the pre-training recipe
     (``--opt adamw``, ``--task_balancer none``: the balancer group is empty, utils/optim_factory.py:138-155)."""
+    _check_adamw_args(args)
+    return _fused(args, model, reducer, args.weight_decay)
+
+
+def _check_adamw_args(args) -> None:
     if getattr(args, 'opt', 'adamw').lower().split('_')[-1] != 'adamw':
         raise ValueError('amd_loop.create_optimizer: the fused step is AdamW (--opt adamw); use the reference factory for other optimisers')
     if getattr(args, 'task_balancer', 'none') != 'none':
         raise ValueError('amd_loop.create_optimizer: --task_balancer uncertainty has trainable balancer weights outside the arena; '
                          'use the reference factory (the drop-in seam still works, at the reference loop\'s speed)')
-    kw = dict(lr=args.lr, weight_decay=args.weight_decay)
+
+
+def _fused(args, model, reducer, weight_decay, groups=None) -> FusedAdamW:
+    kw = dict(lr=args.lr, weight_decay=weight_decay)
     if getattr(args, 'opt_eps', None) is not None:
         kw['eps'] = args.opt_eps
     if getattr(args, 'opt_betas', None) is not None:
         kw['betas'] = tuple(args.opt_betas)
-    opt = FusedAdamW(model, **kw)
+    opt = FusedAdamW(model, groups=groups, **kw) if groups is not None else FusedAdamW(model, **kw)
     reducer = reducer if reducer is not None else getattr(model, '_amd_reducer', None)
     if reducer is not None:
         mdist.attach(model, reducer, opt)
     opt._amd_reducer = reducer
     return opt
+
+
+def _group_rule(model: torch.nn.Module, weight_decay: float, skip_list, get_num_layer, get_layer_scale, decoder_decay, decoder_list,
+                no_lr_scale_list) -> list:
+    """One group per (layer id, decay class, lr-scale exemption), in the order the trainable tensors first open them.
+      decay class   none: a 1-D tensor, a ``.bias`` or a name in ``skip_list``; else ``decoder_decay`` for a ``decoder.*`` name or
+                    one in ``decoder_list`` when ``decoder_decay`` is given; else ``weight_decay``
+      layer id      ``get_num_layer(name)`` (None without it); with it, a name in ``no_lr_scale_list`` gets a group of its own
+      lr_scale      ``get_layer_scale(layer id)`` when given and the group is not exempt, else 1"""
+    groups = {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        if p.ndim == 1 or name.endswith('.bias') or name in skip_list:
+            cls, wd = 'no_decay', 0.
+        elif decoder_decay is not None and (name.startswith('decoder.') or name in decoder_list):
+            cls, wd = 'decoder_decay', decoder_decay
+        else:
+            cls, wd = 'decay', weight_decay
+        layer = get_num_layer(name) if get_num_layer is not None else None
+        exempt = get_num_layer is not None and name in no_lr_scale_list
+        key = (layer, cls, exempt)
+        if key not in groups:
+            scale = get_layer_scale(layer) if get_layer_scale is not None and not exempt else 1.
+            groups[key] = dict(weight_decay=wd, params=[], lr_scale=scale)
+        groups[key]['params'].append(p)
+    return list(groups.values())
+
+
+def finetune_param_groups(args, model: torch.nn.Module, skip_list=None, get_num_layer=None, get_layer_scale=None,
+                          filter_bias_and_bn: bool = True) -> list:
+    """The param groups utils.optim_factory.create_optimizer(args, model, ...) gives a fine-tuning script (the rule of
+    utils/optim_factory.py:51-101 and its caller :105-133): no weight decay for 1-D tensors, biases and the skip list (default
+    ``model.no_weight_decay()``), ``args.decoder_decay`` on ``decoder.*`` and ``model.decoder_weight_decay()``, layer-wise lr
+    scales, and the '-'-separated ``args.no_lr_scale_list`` exempt from them.  ``args.weight_decay == 0`` or
+    ``filter_bias_and_bn=False``: one group of every trainable tensor with ``args.weight_decay``."""
+    if not (args.weight_decay and filter_bias_and_bn):
+        return [dict(params=[p for p in model.parameters() if p.requires_grad], weight_decay=args.weight_decay, lr_scale=1.)]
+    if skip_list is None:
+        skip_list = model.no_weight_decay() if hasattr(model, 'no_weight_decay') else ()
+    decoder_list = model.decoder_weight_decay() if hasattr(model, 'decoder_weight_decay') else ()
+    nls = getattr(args, 'no_lr_scale_list', None)
+    return _group_rule(model, args.weight_decay, skip_list, get_num_layer, get_layer_scale, getattr(args, 'decoder_decay', None),
+                       decoder_list, nls.split('-') if nls is not None else ())
+
+
+def create_optimizer_groups(args, model: torch.nn.Module, skip_list=None, get_num_layer=None, get_layer_scale=None, reducer=None,
+                            filter_bias_and_bn: bool = True) -> FusedAdamW:
+    """Replaces utils.optim_factory.create_optimizer(args, model, skip_list=..., get_num_layer=..., get_layer_scale=...), the
+    module branch every fine-tuning script builds its optimiser with (run_finetuning_cls.py:386-389; the same in _semseg, _depth
+    and _taskonomy): FusedAdamW(groups=finetune_param_groups(...)), one fused library call per step.  The loop's
+    ``g['lr'] = lr_schedule[it] * g['lr_scale']`` and ``g['weight_decay'] = wd_schedule[it]`` (where > 0) act on its groups
+    unchanged (run_finetuning_cls.py:504-508)."""
+    _check_adamw_args(args)
+    groups = finetune_param_groups(args, model, skip_list, get_num_layer, get_layer_scale, filter_bias_and_bn)
+    return _fused(args, model, reducer, 0., groups=groups)
 
 
 class LossScaler:

@@ -61,7 +61,7 @@ extern "C" {
 
 int mmae_abi_version(void);
 /* sizeof the descriptor structs as this build of the library sees them (0 gemm, 1 block, 2 stack, 3 adapter, 4 opt,
- * 5 patch_src, 6 dw_group; -1 for an unknown index): a binding checks its own struct mirrors against these at load time. */
+ * 5 patch_src, 6 dw_group, 7 colsum_job, 8 opt_groups; -1 for an unknown index): a binding checks its own struct mirrors against these at load time. */
 int mmae_struct_size(int which);
 /* last HIP error string seen by this thread's launches (static storage). */
 const char* mmae_last_error(void);
@@ -823,6 +823,37 @@ typedef struct mmae_opt_desc {
     const float* grad_scale_dev;                 /* optional: the loss scale the gradients still carry */
 } mmae_opt_desc;
 int mmae_opt_step(const mmae_opt_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * mmae_opt_step with a learning rate and a weight decay per parameter GROUP: torch.optim.AdamW over the param groups of
+ * the fine-tuning recipes (utils/optim_factory.py:21-101: no decay for biases / 1-D tensors / the skip list, layer-wise lr
+ * decay).  Everything else is mmae_opt_step's: the ONE gradient 2-norm over the whole arena (clip_grad_norm_ over all
+ * parameters), clip / skip, the non-finite guards, GradScaler's found_inf / grad_scale, grad_prescale, the device step counter
+ * and bias corrections, the counters, the shadow write.  state[3..4] record group 0's lr and weight_decay.
+ *   group_map  device u16 [ceil(n / 64)]: the group of every 64-element chunk of the arena (engine.ALIGN = 64 keeps tensors
+ *              apart; a padding chunk may carry any group).  Indices >= n_groups are read as n_groups - 1.
+ *   n_groups   1 .. MMAE_OPT_MAX_GROUPS with hyper; 1 .. 65536 with hyper_dev
+ *   hyper      host f32 [n_groups][2] = (lr, weight_decay), read during the call and passed to the launch by value (eager)
+ *   hyper_dev  device f32 [n_groups][2], read by the kernel (a captured hipGraph replays with the values the host refreshes
+ *              before each replay, as lrwd_dev); when set, hyper is not read.
+ * With one group the results are bit-identical to mmae_opt_step's (the same per-element expressions).  ABI v7.
+ * ------------------------------------------------------------------------- */
+#define MMAE_OPT_MAX_GROUPS 256
+typedef struct mmae_opt_groups_desc {
+    float* p; const float* g; float* m; float* v; int64_t n;
+    void* shadow; int32_t shadow_dtype;
+    float beta1, beta2, eps;
+    float clip_grad, skip_grad, grad_prescale;
+    const float* loss_dev;
+    float* state; int32_t* istate; float* ws;
+    const float* found_inf_dev;
+    const float* grad_scale_dev;
+    const uint16_t* group_map;
+    int32_t n_groups;
+    const float* hyper;
+    const float* hyper_dev;
+} mmae_opt_groups_desc;
+int mmae_opt_step_groups(const mmae_opt_groups_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Truncated depth standardisation, the step right before the model in the training loop

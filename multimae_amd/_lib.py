@@ -114,6 +114,17 @@ class OptDesc(ctypes.Structure):
                 ('state', _P), ('istate', _P), ('ws', _P), ('found_inf_dev', _P), ('grad_scale_dev', _P)]
 
 
+class OptGroupsDesc(ctypes.Structure):
+    """mirror of mmae_opt_groups_desc"""
+    _fields_ = [('p', _P), ('g', _P), ('m', _P), ('v', _P), ('n', _L), ('shadow', _P), ('shadow_dtype', _I),
+                ('beta1', _F), ('beta2', _F), ('eps', _F), ('clip_grad', _F), ('skip_grad', _F), ('grad_prescale', _F),
+                ('loss_dev', _P), ('state', _P), ('istate', _P), ('ws', _P), ('found_inf_dev', _P), ('grad_scale_dev', _P),
+                ('group_map', _P), ('n_groups', _I), ('hyper', _P), ('hyper_dev', _P)]
+
+
+OPT_MAX_GROUPS = 256     # MMAE_OPT_MAX_GROUPS: groups whose (lr, weight_decay) a launch takes by value
+
+
 class PatchSrc(ctypes.Structure):
     """mirror of mmae_patch_src"""
     _fields_ = [
@@ -179,7 +190,8 @@ def load() -> ctypes.CDLL:
         fn.argtypes = argtypes
     if lib.mmae_abi_version() != 7:
         raise RuntimeError('libmmae_hip.so ABI version mismatch')
-    for which, cls in enumerate((GemmDesc, BlockDesc, StackDesc, AdapterDesc, OptDesc, PatchSrc, DwGroupDesc, ColsumJob)):
+    for which, cls in enumerate((GemmDesc, BlockDesc, StackDesc, AdapterDesc, OptDesc, PatchSrc, DwGroupDesc, ColsumJob,
+                                     OptGroupsDesc)):
         if lib.mmae_struct_size(which) != ctypes.sizeof(cls):
             raise RuntimeError(f'{cls.__name__}: ctypes mirror ({ctypes.sizeof(cls)} B) != library struct ({lib.mmae_struct_size(which)} B)')
     if os.environ.get('MMAE_MX_WGRAD') is not None:      # A/B: bf16 (0) or MX-fp8 (1) weight gradients in MX-fp8 mode (ops.mx_wgrad)

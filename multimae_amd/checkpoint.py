@@ -102,8 +102,17 @@ def _trainable(opt):
     return [(n, a.offsets[n], a.sizes[n], a._params[n].shape) for n in a.param_order if a.trainable[n]]
 
 
+def _group_entry(g, ids) -> dict:
+    return {'lr': g['lr'], 'betas': tuple(g['betas']), 'eps': g['eps'], 'weight_decay': g['weight_decay'], 'amsgrad': False,
+            'lr_scale': g.get('lr_scale', 1.0), 'params': ids}
+
+
 def optimizer_state_to_torch(opt) -> dict:
-    """FusedAdamW moments -> ``torch.optim.AdamW.state_dict()`` layout (one param group, state per trainable tensor)."""
+    """FusedAdamW moments -> ``torch.optim.AdamW.state_dict()`` layout (one param group, state per trainable tensor).  A grouped
+    FusedAdamW (``group_names`` set) gives the layout of ``torch.optim.AdamW(groups)``: state indices numbered group by group,
+    each group's tensors in its own order, and every group's hyper-parameters."""
+    if getattr(opt, 'group_names', None) is not None:
+        return _grouped_state_to_torch(opt)
     g = opt.param_groups[0]
     state = {}
     for i, (n, off, size, shape) in enumerate(_trainable(opt)):
@@ -114,9 +123,57 @@ def optimizer_state_to_torch(opt) -> dict:
     return {'state': state, 'param_groups': [group]}
 
 
+def _grouped_state_to_torch(opt) -> dict:
+    a = opt.arena
+    state, groups = {}, []
+    for g, names in zip(opt.param_groups, opt.group_names):
+        ids = []
+        for n in names:
+            off, size, shape = a.offsets[n], a.sizes[n], a._params[n].shape
+            i = len(state)
+            state[i] = {'step': torch.tensor(float(opt.step_count)), 'exp_avg': opt.m[off:off + size].view(shape).clone(),
+                        'exp_avg_sq': opt.v[off:off + size].view(shape).clone()}
+            ids.append(i)
+        groups.append(_group_entry(g, ids))
+    return {'state': state, 'param_groups': groups}
+
+
+def _grouped_state_from_torch(opt, sd: dict) -> None:
+    a, names = opt.arena, opt.group_names
+    sgroups = sd['param_groups']
+    if len(sgroups) != len(names) or any(len(sg['params']) != len(nms) for sg, nms in zip(sgroups, names)):
+        raise ValueError(f'optimizer state has groups of {[len(sg["params"]) for sg in sgroups]} tensors, the optimiser '
+                         f'{[len(nms) for nms in names]}: a different param group layout')
+    step = 0
+    with torch.no_grad():
+        for sg, nms in zip(sgroups, names):
+            for pid, n in zip(sg['params'], nms):
+                off, size, shape = a.offsets[n], a.sizes[n], a._params[n].shape
+                st = sd['state'].get(pid)
+                if st is None:
+                    opt.m[off:off + size].zero_(); opt.v[off:off + size].zero_()
+                    continue
+                if tuple(st['exp_avg'].shape) != tuple(shape):
+                    raise ValueError(f'{n}: moment shape {tuple(st["exp_avg"].shape)} != parameter shape {tuple(shape)}')
+                opt.m[off:off + size].copy_(st['exp_avg'].reshape(-1))
+                opt.v[off:off + size].copy_(st['exp_avg_sq'].reshape(-1))
+                step = max(step, int(float(st['step'])))
+    opt.step_count = step
+    for g, sg in zip(opt.param_groups, sgroups):
+        for k in ('lr', 'weight_decay', 'eps', 'lr_scale'):
+            if k in sg:
+                g[k] = sg[k]
+        if 'betas' in sg:
+            g['betas'] = tuple(sg['betas'])
+
+
 def optimizer_state_from_torch(opt, sd: dict) -> None:
     """Load a ``torch.optim.AdamW`` state dict (e.g. from a reference checkpoint) into FusedAdamW's flat moments.  Extra param
-    groups (the reference's loss-balancer group) are ignored; the schedule values are taken from group 0."""
+    groups (the reference's loss-balancer group) are ignored; the schedule values are taken from group 0.  A grouped FusedAdamW
+    takes a state of exactly its own group layout (same number of groups and of tensors in each), every group's values."""
+    if getattr(opt, 'group_names', None) is not None:
+        _grouped_state_from_torch(opt, sd)
+        return
     tr = _trainable(opt)
     ids = sd['param_groups'][0]['params']
     if len(ids) != len(tr):

@@ -592,6 +592,78 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// Per-group (lr, weight_decay) of mmae_opt_step_groups: in the kernel arguments (eager) or in device memory (hipGraph replay).
+struct GroupHyperVal {
+    float v[2 * MMAE_OPT_MAX_GROUPS];
+    __device__ __forceinline__ void get(int k, float& lr, float& wd) const { lr = v[2 * k]; wd = v[2 * k + 1]; }
+};
+struct GroupHyperDev {
+    const float* __restrict__ v;
+    __device__ __forceinline__ void get(int k, float& lr, float& wd) const { lr = v[2 * k]; wd = v[2 * k + 1]; }
+};
+
+// adamw_kernel with the group of every 64-element chunk looked up once per 16 B run (a run never straddles a chunk).
+// The per-element expressions are adamw_kernel's with the fused multiply-adds written out as the compiler contracts them
+// there (its lr / weight decay are uniform, these per chunk, which lets the compiler pick other products to fuse): the
+// vector path and the scalar tail of adamw_kernel contract differently, and so do these, so one group gives adamw_kernel's
+// results bit for bit.  bc[0..1] = 1 - beta1^t, sqrt(1 - beta2^t) from opt_finalize_kernel.
+template <typename ST, typename HY>
+__global__ void __launch_bounds__(256) adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, long long n, const uint16_t* __restrict__ gmap,
+                                                           int n_groups, const HY hy, float b1, float b2, float eps,
+                                                           const float* __restrict__ bc, const float* __restrict__ grad_scale,
+                                                           const int* __restrict__ skip, ST* __restrict__ shadow) {
+    if (skip && *skip) return;
+    const float bc1 = bc[0], bc2_sqrt = bc[1];
+    const float gs = grad_scale ? *grad_scale : 1.f;
+    for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long long)gridDim.x * 1024) {
+        float lr, wd;
+        if (i + 4 <= n) {
+            // the map entry is loaded before the data so that waiting for it leaves the four 16 B loads in flight
+            const int k = gmap[i >> 6];
+            f32x4 pv = ld4(p + i), mv = ld4(m + i), vv = ld4(v + i);
+            const f32x4 gv = ld4(g + i);
+            hy.get(k < n_groups ? k : n_groups - 1, lr, wd);
+            const float decay = fmaf(-lr, wd, 1.f), step = lr / bc1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gj = gv[j] * gs;
+                mv[j] = fmaf(b1, mv[j], (1.f - b1) * gj);
+                vv[j] = fmaf(b2, vv[j], (1.f - b2) * gj * gj);
+                const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
+                pv[j] = fmaf(decay, pv[j], -(step * (mv[j] / denom)));
+            }
+            st4(p + i, pv); st4(m + i, mv); st4(v + i, vv);
+            if (shadow) st4(shadow + i, pv);
+        } else {
+            for (long long j = i; j < n; ++j) {
+                const int k = gmap[j >> 6];
+                hy.get(k < n_groups ? k : n_groups - 1, lr, wd);
+                const float gj = g[j] * gs;
+                const float mj = fmaf(1.f - b1, gj, b1 * m[j]), vj = fmaf(gj, (1.f - b2) * gj, b2 * v[j]);
+                const float pj = fmaf(fmaf(-lr, wd, 1.f), p[j], -((lr / bc1) * (mj / (sqrtf(vj) / bc2_sqrt + eps))));
+                p[j] = pj; m[j] = mj; v[j] = vj;
+                if (shadow) ActT<ST>::st(shadow + j, pj);
+            }
+        }
+    }
+}
+
+template <typename HY>
+int launch_adamw_groups(const mmae_opt_groups_desc* d, const HY& hy, hipStream_t st) {
+    long long nb = cdiv64(d->n, 1024);
+    if (nb > 8192) nb = 8192;
+    const float* bc = d->state + 5;
+    const float* gsc = d->state + 2;
+    if (d->shadow && d->shadow_dtype == MMAE_BF16)
+        hipLaunchKernelGGL((adamw_groups_kernel<uint16_t, HY>), dim3((unsigned)nb), dim3(256), 0, st, d->p, d->g, d->m, d->v, (long long)d->n,
+                           d->group_map, (int)d->n_groups, hy, d->beta1, d->beta2, d->eps, bc, gsc, (const int*)d->istate, (uint16_t*)d->shadow);
+    else
+        hipLaunchKernelGGL((adamw_groups_kernel<float, HY>), dim3((unsigned)nb), dim3(256), 0, st, d->p, d->g, d->m, d->v, (long long)d->n,
+                           d->group_map, (int)d->n_groups, hy, d->beta1, d->beta2, d->eps, bc, gsc, (const int*)d->istate, (float*)d->shadow);
+    return mmae_check_launch("adamw_groups");
+}
+
 }  // namespace
 
 extern "C" {
@@ -782,6 +854,27 @@ int mmae_opt_step(const mmae_opt_desc* d, void* stream) {
     if ((rc = mmae_check_launch("opt_finalize"))) return rc;
     return mmae_adamw_dev(d->p, d->g, d->m, d->v, d->n, d->state + 3, d->beta1, d->beta2, d->eps, d->state + 2, d->istate, d->shadow,
                           d->shadow_dtype, stream);
+}
+
+int mmae_opt_step_groups(const mmae_opt_groups_desc* d, void* stream) {
+    MMAE_REQUIRE(d && d->p && d->g && d->m && d->v && d->n > 0 && d->state && d->istate && d->ws && d->group_map,
+                 "opt_step_groups: bad argument");
+    MMAE_REQUIRE(d->grad_prescale > 0.f, "opt_step_groups: grad_prescale must be positive (1 for a single process)");
+    MMAE_REQUIRE(d->hyper_dev ? (d->n_groups >= 1 && d->n_groups <= 65536) : (d->hyper && d->n_groups >= 1 && d->n_groups <= MMAE_OPT_MAX_GROUPS),
+                 "opt_step_groups: n_groups out of range, or neither hyper nor hyper_dev given");
+    MMAE_REQUIRE(((uintptr_t)d->p % 16 == 0) && ((uintptr_t)d->g % 16 == 0) && ((uintptr_t)d->m % 16 == 0) && ((uintptr_t)d->v % 16 == 0)
+                 && ((uintptr_t)d->group_map % 2 == 0), "opt_step_groups: unaligned");
+    int rc = mmae_sumsq(d->g, d->n, d->state, d->ws, stream);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const float lr0 = d->hyper_dev ? 0.f : d->hyper[0], wd0 = d->hyper_dev ? 0.f : d->hyper[1];
+    hipLaunchKernelGGL(opt_finalize_kernel, dim3(1), dim3(1), 0, st, d->state, d->istate, lr0, wd0, d->hyper_dev, d->beta1, d->beta2,
+                       d->clip_grad, d->skip_grad, d->grad_prescale, d->loss_dev, d->found_inf_dev, d->grad_scale_dev);
+    if ((rc = mmae_check_launch("opt_finalize"))) return rc;
+    if (d->hyper_dev) return launch_adamw_groups(d, GroupHyperDev{d->hyper_dev}, st);
+    GroupHyperVal hv;
+    for (int k = 0; k < 2 * MMAE_OPT_MAX_GROUPS; ++k) hv.v[k] = k < 2 * d->n_groups ? d->hyper[k] : 0.f;
+    return launch_adamw_groups(d, hv, st);
 }
 
 }  // extern "C"

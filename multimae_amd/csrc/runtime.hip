@@ -179,6 +179,7 @@ int mmae_struct_size(int which) {
         case 5: return (int)sizeof(mmae_patch_src);
         case 6: return (int)sizeof(mmae_dw_group_desc);
         case 7: return (int)sizeof(mmae_colsum_job);
+        case 8: return (int)sizeof(mmae_opt_groups_desc);
         default: return -1;
     }
 }

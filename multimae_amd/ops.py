@@ -15,7 +15,7 @@ import torch
 from . import _lib
 import contextlib
 
-from ._lib import BF16, F16, F32, F32X3, F32F16, MXFP8, EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_G, EPI_MUL, AdapterDesc, BlockDesc, DwGroupDesc, GemmDesc, OptDesc, PatchSrc, StackDesc, check
+from ._lib import BF16, F16, F32, F32X3, F32F16, MXFP8, EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_G, EPI_MUL, AdapterDesc, BlockDesc, DwGroupDesc, GemmDesc, OptDesc, OptGroupsDesc, PatchSrc, StackDesc, check
 
 Tensor = torch.Tensor
 
@@ -1432,3 +1432,34 @@ def opt_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, istate: 
     assert state.dtype == torch.float32 and state.numel() >= 8 and istate.dtype == torch.int32 and istate.numel() >= 8
     d.state, d.istate, d.ws = state.data_ptr(), istate.data_ptr(), ws.data_ptr()
     check(_lib.load().mmae_opt_step(ctypes.byref(d), _stream()), 'opt_step')
+
+
+def opt_step_groups(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, istate: Tensor, ws: Tensor, *, group_map: Tensor,
+                    n_groups: int, hyper: Optional[Sequence[float]] = None, hyper_dev: Optional[Tensor] = None, beta1: float,
+                    beta2: float, eps: float, clip_grad: Optional[float], skip_grad: Optional[float], grad_prescale: float = 1.0,
+                    loss_dev: Optional[Tensor] = None, shadow: Optional[Tensor] = None, found_inf_dev: Optional[Tensor] = None,
+                    grad_scale_dev: Optional[Tensor] = None) -> None:
+    """mmae_opt_step_groups: opt_step with a (lr, weight_decay) per parameter group.  ``group_map``: int16 (read as uint16)
+    [ceil(n / 64)], the group of every 64-element chunk.  ``hyper``: host [lr_0, wd_0, lr_1, wd_1, ...], passed to the launch by
+    value (at most OPT_MAX_GROUPS groups); ``hyper_dev``: the same as a device f32 [n_groups, 2] tensor (hipGraph replay)."""
+    n = p.numel()
+    assert group_map.dtype == torch.int16 and group_map.numel() == (n + 63) // 64, 'group_map: int16 [ceil(n / 64)]'
+    assert (hyper is None) != (hyper_dev is None), 'give exactly one of hyper / hyper_dev'
+    assert state.dtype == torch.float32 and state.numel() >= 8 and istate.dtype == torch.int32 and istate.numel() >= 8
+    d = OptGroupsDesc()
+    d.p, d.g, d.m, d.v, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n
+    d.shadow, d.shadow_dtype = _p(shadow), (dcode(shadow.dtype) if shadow is not None else F32)
+    d.beta1, d.beta2, d.eps = beta1, beta2, eps
+    d.clip_grad, d.skip_grad, d.grad_prescale = (clip_grad or 0.0), (skip_grad or 0.0), grad_prescale
+    d.loss_dev, d.found_inf_dev, d.grad_scale_dev = _p(loss_dev), _p(found_inf_dev), _p(grad_scale_dev)
+    d.state, d.istate, d.ws = state.data_ptr(), istate.data_ptr(), ws.data_ptr()
+    d.group_map, d.n_groups = group_map.data_ptr(), int(n_groups)
+    host = None
+    if hyper_dev is not None:
+        assert hyper_dev.dtype == torch.float32 and hyper_dev.numel() == 2 * n_groups
+        d.hyper_dev = hyper_dev.data_ptr()
+    else:
+        assert len(hyper) == 2 * n_groups and n_groups <= _lib.OPT_MAX_GROUPS
+        host = (ctypes.c_float * len(hyper))(*hyper)       # copied into the launch's arguments during the call
+        d.hyper = ctypes.addressof(host)
+    check(_lib.load().mmae_opt_step_groups(ctypes.byref(d), _stream()), 'opt_step_groups')
