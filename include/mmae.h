@@ -88,7 +88,9 @@ const char* mmae_last_error(void);
  *            the composite encoder / decoder calls use this pair for bf16 activations).  Same kernels and restrictions.
  * bf16 operands need lda/ldb % 8 == 0 and 16-byte aligned bases; a k-contiguous
  * operand may have any K as long as the bytes up to the next multiple of 8 along
- * k are readable and finite*0-safe (the engine zero-pads).
+ * k are readable and finite, and zero in at least one of the two operands: both
+ * k-contiguous operands' padding enters the products, so junk x junk would reach C
+ * (a k-strided operand's rows past K are never read; the engine zero-pads).
  * ------------------------------------------------------------------------- */
 #define MMAE_EPI_NONE  0
 #define MMAE_EPI_GELU  1

@@ -88,3 +88,197 @@ def make_inputs(doms, B, S):
 def rel_err(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+# ----------------------------------------------------------------------------------------------
+# Element-wise checks.  rel_err is one number over the whole output: an error confined to a tile tail, one row or one element
+# drowns in a norm over a million elements (tests/test_check_helpers_cpu.py records cases it passes).  The helpers below bound
+# every element on its own, in fp64, and guard the memory around an output.
+
+# significand bits (hidden bit included) and the smallest normal exponent of each storage format
+_FMT = {torch.bfloat16: (8, -126), torch.float16: (11, -14), torch.float32: (24, -126)}
+
+
+def unit_roundoff(dtype) -> float:
+    """u = 2^-p: round-to-nearest into `dtype` moves a value by at most u times its magnitude (normal range)."""
+    return 2.0 ** -_FMT[dtype][0]
+
+
+def gamma(n, u: float = 2.0 ** -24) -> float:
+    """gamma_n = n u / (1 - n u): bound on the relative error of any order of summation of n terms (Higham, Accuracy and Stability
+    of Numerical Algorithms, Lemma 3.1) -- with u = 2^-24 the fp32 accumulation every kernel here does."""
+    return n * u / (1.0 - n * u)
+
+
+def ulp(dtype, x):
+    """Spacing of `dtype` numbers at |x| (fp64 tensor of x's shape): 2^(e - p + 1) with e = floor(log2 |x|), clamped to the
+    subnormal spacing below the normal range.  A rounding to nearest moves a value by at most half of it."""
+    p, emin = _FMT[dtype]
+    x = torch.as_tensor(x).double().abs()
+    e = torch.floor(torch.log2(x.clamp_min(2.0 ** emin))).clamp_min(emin)
+    return torch.exp2(e - (p - 1))
+
+
+def prod_bound(absA, absB, K: int, out_dtype=None, ref=None, u_op: float = 0.0, extra=None):
+    """Element-wise error bound of C = A . B^T [M, K] x [N, K] computed with fp32 accumulation and stored as `out_dtype`:
+        gamma_K (|A| |B|^T)          any summation order of K exact products in fp32 (split-K slabs and their sum included)
+      + u_op (|A| |B|^T)             operands rounded inside the product (split-bf16 / fp16 operands; 0 when they are exact)
+      + extra                        caller's epilogue terms (already an absolute bound)
+      + ulp(out_dtype, |ref| + all)  the final rounding (half an ulp at the computed value <= one ulp at the reference's)
+    absA [M, K], absB [N, K] non-negative; computed in fp64 on their device."""
+    t = absA.double() @ absB.double().t()
+    b = (gamma(K) + u_op) * t
+    if extra is not None:
+        b = b + extra
+    if out_dtype is not None and ref is not None:
+        b = b + ulp(out_dtype, ref.double().abs() + b)
+    return b
+
+
+def _fmt_index(idx, names):
+    if names is None:
+        return str(tuple(idx))
+    return '(' + ', '.join(f'{n}={i}' for n, i in zip(names, idx)) + ')'
+
+
+def assert_within(out, ref, bound, what: str, names=None):
+    """|out - ref| <= bound element by element, in fp64 (a NaN / inf in out is a violation).  On failure: how many elements
+    violate the bound, the worst one (largest |out - ref| / bound) by index -- (row, col), or (b, h, q, d) with names=('b', 'h',
+    'q', 'd') -- with its value, reference and bound."""
+    o = out.detach().double()
+    r = ref.detach().double().to(o.device)
+    bd = torch.as_tensor(bound).double().to(o.device).expand_as(r)
+    err = (o - r).abs()
+    bad = ~(err <= bd)
+    n = int(bad.sum())
+    if n == 0:
+        return
+    ratio = torch.where(torch.isfinite(err), err / bd.clamp_min(1e-300), torch.full_like(err, float('inf')))
+    ratio = torch.where(bad, ratio, torch.zeros_like(ratio))
+    flat = int(torch.argmax(torch.nan_to_num(ratio, nan=float('inf'))))
+    idx = np.unravel_index(flat, tuple(r.shape))
+    raise AssertionError(f'{what}: {n} of {r.numel()} elements outside the bound; worst at {_fmt_index(idx, names)}: '
+                         f'value {float(o.reshape(-1)[flat])!r}, reference {float(r.reshape(-1)[flat])!r}, bound {float(bd.reshape(-1)[flat]):.3e}')
+
+
+# ----------------------------------------------------------------------------------------------
+# Guarded outputs and poisoned operands
+_INT_OF = {1: torch.uint8, 2: torch.int16, 4: torch.int32}
+# the sentinel: bytes a5 ff repeated -- a NaN as bf16 / fp16 (0xffa5) and as f32 (0xffa5ffa5)
+_SENT = {2: -91, 4: -5898331}                      # int16 0xffa5, int32 0xffa5ffa5
+
+
+class Guarded:
+    """One flat allocation that holds the logical [rows][cols] view with leading dimension ld >= cols, `guard` elements of
+    guard zone before it and after it.  Every element outside the view holds a fixed sentinel bit pattern (a NaN in every
+    float format here); intact() asserts that all of them still do, bit for bit.  Pass `flat` with element offset `off` (or
+    `full` / `view`, which start at the view) to the code under test."""
+
+    def __init__(self, rows: int, cols: int, ld: int, dtype, device, guard: int = 64, fill=None):
+        assert ld >= cols and guard % 8 == 0 and ld > 0
+        self.rows, self.cols, self.ld, self.dtype, self.off = rows, cols, ld, dtype, guard
+        self.esz = torch.empty((), dtype=dtype).element_size()
+        n = guard + rows * ld + guard
+        self.flat = torch.empty((n,), dtype=dtype, device=device)
+        self._bits().fill_(_SENT[self.esz])
+        self.full = self.flat[guard:guard + rows * ld].view(rows, ld)
+        self.view = self.full[:, :cols]
+        if fill is not None:
+            self.view.copy_(fill)
+        m = torch.ones((n,), dtype=torch.bool, device=device)
+        m[guard:guard + rows * ld].view(rows, ld)[:, :cols] = False
+        self._outside = m
+
+    def _bits(self):
+        return self.flat.view(_INT_OF[self.esz])
+
+    def intact(self, what: str = 'guarded buffer'):
+        bits = self._bits()
+        bad = self._outside & (bits != _SENT[self.esz])
+        n = int(bad.sum())
+        if n:
+            i = int(torch.nonzero(bad)[0])
+            if i < self.off:
+                where = f'guard zone before the view, element {i - self.off}'
+            elif i >= self.off + self.rows * self.ld:
+                where = f'guard zone after the view, element {i - self.off - self.rows * self.ld}'
+            else:
+                where = f'(row {(i - self.off) // self.ld}, col {(i - self.off) % self.ld}) of the ld padding'
+            raise AssertionError(f'{what}: {n} element(s) outside the [{self.rows}][{self.cols}] view (ld {self.ld}) were written; '
+                                 f'first at {where}')
+
+
+def poisoned(X, ld: int, dtype, device, *, finite_to: int = 0, junk: float = 0.0, col0: int = 8, nan_rows: int = 8):
+    """X [rows][cols] placed at column `col0` of a flat buffer with row stride ld (returns (flat, offset of X[0][0], ld)).  Columns
+    cols .. finite_to hold `junk` (finite, the bytes a kernel may read past a ragged contraction edge: mmae.h's bf16 rule rounds
+    reads up to the next multiple of 8 along k), every other element of the buffer -- the rest of the ld padding, the col0 columns
+    in front of each row, nan_rows rows after the last one and ld elements before the first -- is NaN."""
+    rows, cols = X.shape
+    assert col0 + max(cols, finite_to) <= ld
+    flat = torch.full(((rows + nan_rows + 1) * ld,), float('nan'), dtype=dtype, device=device)
+    off = ld + col0
+    v = flat[ld:ld + rows * ld].view(rows, ld)
+    v[:, col0:col0 + cols] = X.to(device=device, dtype=dtype)
+    if finite_to > cols:
+        v[:, col0 + cols:col0 + finite_to] = junk
+    return flat, off
+
+
+def attention_bounds(q, k, v, do, scale: float, *, u_in: float, u_p: float, out_dtype, grad_dtype=None, eta_p: float = 0.0,
+                     eta_ds: float = 0.0):
+    """fp64 references and element-wise error bounds of one attention forward (o, lse) and backward (dq, dk, dv) on the operands
+    exactly as the kernel sees them: q, do [Z, Nq, hd], k, v [Z, Nk, hd] (Z = batch x heads).
+      u_in  relative error of ONE product of two operands inside the kernel's matrix products (0 for bf16 / fp16 operands, which
+            multiply exactly into fp32; the caller states it for split or rounded f32 operands)
+      u_p   unit roundoff of the type P -- and in the backward dS -- is rounded to before its product (attention.hip: 'P and dS right
+            before their MFMA'; the GEMM path stores P / dS in the activation type)
+      eta_p, eta_ds  the absolute floor of that rounding for P (<= 1) and dS: fp16 flushes below its smallest subnormal, so a rounding
+            moves x by u |x| + 2^-25 (x in the units the kernel rounds in); 0 for bf16 / f32, whose range reaches e^-88
+    Derivation (fp32 accumulation everywhere, gamma_n as in gamma()):
+      scores  |ds_ij| <= e_i = (u_in + gamma_hd + 4 * 2^-24) * scale * max_j |q_i| . |k_j|   (products + sum + scale / log2 e multiplies)
+      P       every score of row i moves by <= e_i, so softmax entries move by a factor within exp(+-2 e_i); the normaliser's fp32 sum adds
+              gamma_Nk, v_exp_f32 2^-22:  rho_i = exp(2 e_i) - 1 + gamma_Nk + 2^-22
+      o       |do_| <= (rho_i + u_p + u_in + gamma_Nk) (P |V|) + eta_p sum_j |V_j| + ulp(out_dtype)
+      lse     |dlse| <= e_i + gamma_Nk + 8 ulp_f32(|lse| + 1)   (max * ln 2 and __logf in fp32)
+      bwd P   recomputed from the stored lse and read rounded by the GEMM path's softmax backward:
+              rb_i = exp(2 e_i + dlse_i) - 1 + u_p + 2^-22
+      dP      |ddP_ij| <= (u_in + gamma_hd) |dO_i| . |V_j| = EdP_ij;   delta_i = sum_j P_ij dP_ij:
+              |ddelta_i| <= sum_j P_ij (rb_i |dP_ij| + EdP_ij) + gamma_Nk sum_j P_ij |dP_ij|
+      dS      |ddS_ij| <= (rb_i P_ij + eta_p) |dP_ij - delta_i| + P_ij (EdP_ij + |ddelta_i|), then rounded: + u_p (|dS_ij| + that) + eta_ds
+      dq      scale (EdS |K| + (u_in + gamma_Nk) (|dS| + EdS) |K|) + ulp(grad_dtype);  dk the same with dS^T, Q
+      dv      ((rb_i + u_p + u_in + gamma_Nq) P + eta_p)^T |dO| + ulp(grad_dtype)"""
+    grad_dtype = grad_dtype or out_dtype
+    q, k, v, do = (t.double() for t in (q, k, v, do))
+    Nq, hd = q.shape[-2:]
+    Nk = k.shape[-2]
+    u32 = 2.0 ** -24
+    s = scale * (q @ k.transpose(-1, -2))
+    lse = torch.logsumexp(s, -1)
+    P = torch.exp(s - lse[..., None])
+    qk = q.abs() @ k.abs().transpose(-1, -2)
+    e = (u_in + gamma(hd) + 4 * u32) * scale * qk.amax(-1)                   # [Z, Nq]
+    rho = torch.expm1(2 * e) + gamma(Nk) + 2.0 ** -22
+    o = P @ v
+    pv = P @ v.abs()
+    b_o = (rho + u_p + u_in + gamma(Nk))[..., None] * pv + eta_p * v.abs().sum(-2, keepdim=True)
+    b_o = b_o + ulp(out_dtype, o.abs() + b_o)
+    b_lse = e + gamma(Nk) + 8 * ulp(torch.float32, lse.abs() + 1)
+    dP = do @ v.transpose(-1, -2)
+    delta = (P * dP).sum(-1)
+    dS = P * (dP - delta[..., None])
+    dq = scale * (dS @ k)
+    dk = scale * (dS.transpose(-1, -2) @ q)
+    dv = P.transpose(-1, -2) @ do
+    rb = (torch.expm1(2 * e + b_lse) + u_p + 2.0 ** -22)[..., None]
+    EdP = (u_in + gamma(hd)) * (do.abs() @ v.abs().transpose(-1, -2))
+    Ed = (P * (rb * dP.abs() + EdP)).sum(-1) + gamma(Nk) * (P * dP.abs()).sum(-1)
+    EdS = (rb * P + eta_p) * (dP - delta[..., None]).abs() + P * (EdP + Ed[..., None])
+    EdS = EdS + u_p * (dS.abs() + EdS) + eta_ds
+    aS = dS.abs() + EdS
+    b_dq = scale * (EdS @ k.abs() + (u_in + gamma(Nk)) * (aS @ k.abs()))
+    b_dk = scale * (EdS.transpose(-1, -2) @ q.abs() + (u_in + gamma(Nq)) * (aS.transpose(-1, -2) @ q.abs()))
+    b_dv = ((rb + u_p + u_in + gamma(Nq)) * P + eta_p).transpose(-1, -2) @ do.abs()
+    b_dq = b_dq + ulp(grad_dtype, dq.abs() + b_dq)
+    b_dk = b_dk + ulp(grad_dtype, dk.abs() + b_dk)
+    b_dv = b_dv + ulp(grad_dtype, dv.abs() + b_dv)
+    return dict(o=(o, b_o), lse=(lse, b_lse), dq=(dq, b_dq), dk=(dk, b_dk), dv=(dv, b_dv), P=P)

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 import multimae_oracle as orc
-from helpers import load_masks_base, load_mini, rel_err
+from helpers import (Guarded, assert_within, attention_bounds, gamma, load_masks_base, load_mini, poisoned, prod_bound, rel_err,
+                     ulp)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -46,7 +47,26 @@ def test_probe_tr16_semantics():
 
 
 # ----------------------------------------------------------------------------------------------
-def _gemm_case(dtype, M, N, K, a_trans, b_trans, *, tile=0, seed=0):
+# split-bf16 ("x3") products: each f32 operand is carried to 2^-16 of itself by hi + lo (lo = the bf16 rounding of the residual), and the
+# dropped lo . lo term is another 2^-16 of |a b|: 3 x 2^-16 per product, rounded up to 2^-14
+U_X3 = 2.0 ** -14
+
+
+def _operand(X, trans, dtype, k_fill):
+    """X [rows][K] as the kernel's operand: k-contiguous (trans False) in a poisoned buffer whose ragged k edge up to the next multiple
+    of 8 holds k_fill (mmae.h: readable, finite, zero in at least one of the two operands), or stored transposed [K][rows] (rows
+    contiguous, every element past rows NaN).  Returns (flat, offset, ld)."""
+    pad = lambda n: (n + 7) // 8 * 8
+    if trans:
+        ld = pad(X.shape[0]) + 16
+        f, off = poisoned(X.t(), ld, dtype, DEV)
+    else:
+        ld = pad(X.shape[1]) + 16
+        f, off = poisoned(X, ld, dtype, DEV, finite_to=pad(X.shape[1]), junk=k_fill)
+    return f, off, ld
+
+
+def _gemm_case(dtype, M, N, K, a_trans, b_trans, *, tile=0, seed=0, u_op=0.0):
     from multimae_amd import ops
     g = torch.Generator().manual_seed(seed)
     A = torch.randn(M, K, generator=g)
@@ -55,20 +75,21 @@ def _gemm_case(dtype, M, N, K, a_trans, b_trans, *, tile=0, seed=0):
         A, B = bf(A).float(), bf(B).float()
     ref = A.double() @ B.double().t()
     pad = lambda n: (n + 7) // 8 * 8
-    if a_trans:
-        As = torch.zeros(K, pad(M)); As[:, :M] = A.t(); lda = pad(M)
-    else:
-        As = torch.zeros(M, pad(K)); As[:, :K] = A; lda = pad(K)
-    if b_trans:
-        Bs = torch.zeros(K, pad(N)); Bs[:, :N] = B.t(); ldb = pad(N)
-    else:
-        Bs = torch.zeros(N, pad(K)); Bs[:, :K] = B; ldb = pad(K)
-    C = torch.full((M, pad(N)), float('nan'), device=DEV)
-    ops.gemm(As.to(DEV, dtype), Bs.to(DEV, dtype), C, M, N, K, lda=lda, ldb=ldb, ldc=pad(N), a_trans=a_trans, b_trans=b_trans, tile=tile)
+    # NaN wherever the kernel must not read; finite junk on the ragged k edge of one operand (alternating with the seed), zeros in the other's
+    # (a transposed operand's rows past K are never read: the other one may carry the junk then)
+    ja = 0.0 if a_trans else 3.0 if b_trans or seed % 2 == 0 else 0.0
+    jb = 0.0 if ja else -5.0
+    Af, ao, lda = _operand(A, a_trans, dtype, ja)
+    Bf, bo, ldb = _operand(B, b_trans, dtype, jb)
+    C = Guarded(M, N, pad(N) + 8, torch.float32, DEV)
+    ops.gemm(Af, Bf, C.flat, M, N, K, lda=lda, ldb=ldb, ldc=C.ld, a_trans=a_trans, b_trans=b_trans, a_off=ao, b_off=bo, c_off=C.off, tile=tile)
     torch.cuda.synchronize()
-    out = C[:, :N].cpu().double()
+    C.intact(f'C of {M}x{N}x{K} tile {tile}')
+    out = C.view.double()
     assert torch.isfinite(out).all()
-    return float((out - ref).norm() / ref.norm())
+    assert_within(out, ref.to(DEV), prod_bound(A.abs().to(DEV), B.abs().to(DEV), K, torch.float32, ref.to(DEV), u_op=u_op),
+                  f'{M}x{N}x{K} a_trans={a_trans} b_trans={b_trans} tile {tile}')
+    return float((out.cpu() - ref).norm() / ref.norm())
 
 
 @pytest.mark.parametrize('a_trans,b_trans', [(False, False), (False, True), (True, False), (True, True)])
@@ -108,9 +129,136 @@ def test_gemm_f32x3_layouts(shape, a_trans, b_trans):
     from multimae_amd import ops
     M, N, K = shape
     with ops.f32_gemm_mode('x3'):
-        err = _gemm_case(torch.float32, M, N, K, a_trans, b_trans)
+        err = _gemm_case(torch.float32, M, N, K, a_trans, b_trans, u_op=U_X3)
     assert err < 2e-5, err
     assert err > 1e-7            # (sanity: this really is the split path, not the exact-f32 kernel)
+
+
+# ----------------------------------------------------------------------------------------------
+# Index probes: one operand one-hot along k, so that every element of C is ONE product -- exact in fp32 and in bf16 -- and C must equal
+# an element of the other operand bit for bit.  A wrong row, column, k index, offset, stride or tail shows up as a wrong value.
+_PROBE_SHAPES = [(1, 3, 1), (129, 131, 33), (257, 255, 71), (321, 258, 100), (64, 520, 257)]
+
+
+def _probe(M, N, K, a_trans, b_trans, dtype, hot, c_dtype, tile=0, f32_as=None):
+    from multimae_amd import ops
+    g = torch.Generator().manual_seed(M * 7 + N * 3 + K)
+    R = bf(torch.randn(max(M, N), K, generator=g)).float()             # bf16 values: exact in every operand format here
+    n_hot = M if hot == 'A' else N
+    pi = (torch.arange(n_hot) * 7 + 3) % K
+    pi[-1] = K - 1                                                     # the last k of the ragged edge
+    H1 = torch.zeros(n_hot, K)
+    H1[torch.arange(n_hot), pi] = 1.0
+    A, B = (H1, R[:N]) if hot == 'A' else (R[:M], H1)
+    want = (R[:N][:, pi].t() if hot == 'A' else R[:M][:, pi]).contiguous()          # C[m, n] = B[n, pi(m)]  |  A[m, pi(n)]
+    ja = 0.0 if a_trans else 3.0
+    jb = 0.0 if (ja or b_trans) else -5.0
+    Af, ao, lda = _operand(A, a_trans, dtype, ja)
+    Bf, bo, ldb = _operand(B, b_trans, dtype, jb)
+    C = Guarded(M, N, (N + 7) // 8 * 8 + 8, c_dtype, DEV)
+    ops.gemm(Af, Bf, C.flat, M, N, K, lda=lda, ldb=ldb, ldc=C.ld, a_trans=a_trans, b_trans=b_trans, a_off=ao, b_off=bo, c_off=C.off,
+             tile=tile, f32_as=f32_as)
+    torch.cuda.synchronize()
+    what = f'{hot}-hot {M}x{N}x{K} a_trans={a_trans} b_trans={b_trans} tile {tile} C {c_dtype}'
+    C.intact(what)
+    assert_within(C.view, want.to(DEV), 0.0, what)
+
+
+@pytest.mark.parametrize('a_trans,b_trans', [(False, False), (False, True), (True, False), (True, True)])
+def test_gemm_bf16_index_probe_bit_exact(a_trans, b_trans):
+    """Every production tile code (1-10), M / N / K on both sides of the tile edges (N not a multiple of 4 or 8, K not one of 8 or 32),
+    operands at nonzero offsets in NaN-poisoned buffers, C at an offset in a guarded buffer with ldc > N: C bit-equal to the
+    selected operand elements, f32 and bf16 C, nothing written outside C's view."""
+    for M, N, K in _PROBE_SHAPES:
+        for tile in range(1, 11):
+            for hot in ('A', 'B'):
+                for c_dtype in (torch.float32, torch.bfloat16):
+                    _probe(M, N, K, a_trans, b_trans, torch.bfloat16, hot, c_dtype, tile=tile)
+
+
+@pytest.mark.parametrize('a_trans,b_trans', [(False, False), (False, True), (True, False), (True, True)])
+def test_gemm_f32_index_probe_bit_exact(a_trans, b_trans):
+    """The same probe on the exact-f32 kernel and the split-bf16 (x3) kernel: bf16-valued operands split into hi + lo = hi + 0, so
+    both products are exact too."""
+    from multimae_amd import ops
+    from multimae_amd._lib import F32X3
+    for M, N, K in _PROBE_SHAPES:
+        for hot in ('A', 'B'):
+            _probe(M, N, K, a_trans, b_trans, torch.float32, hot, torch.float32)
+            _probe(M, N, K, a_trans, b_trans, torch.float32, hot, torch.float32, f32_as=F32X3)
+
+
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('geom', [(2, 3, 33, 65, 32), (1, 2, 197, 196, 64), (2, 2, 64, 1, 32)])
+def test_gemm_batched_strided_attention_forms(geom):
+    """mmae_gemm's batched form (batch, batch_inner, sA / sB / sC, a_off / b_off / c_off) called directly, in the four shapes the
+    attention 'gemm' path issues (ops.attention_fwd / attention_bwd): S = Q K^T over packed qkv / kv rows, O = P V into the head columns
+    of a packed output, dV = P^T dO and dK = dS^T Q into the column slices of a packed dk | dv.  Operands have NaN columns past the
+    packed width, P / dS hold finite junk in the Np - Nk padding columns (the GEMM must not let it reach a stored element), outputs sit in
+    guarded buffers: per element against the fp64 product, and a single-head launch leaves the other heads' columns untouched."""
+    from multimae_amd import ops
+    B, H, Nq, Nk, hd = geom
+    D, Np, Z = H * hd, (Nk + 7) // 8 * 8, B * H
+    g = torch.Generator().manual_seed(Nq * Nk)
+    rnd = lambda *s: bf(torch.randn(*s, generator=g)).float()
+    ldq, ldkv = 3 * D + 16, 2 * D + 16
+    qkv = torch.full((B * Nq, ldq), float('nan')); qkv[:, :3 * D] = rnd(B * Nq, 3 * D)
+    kv = torch.full((B * Nk, ldkv), float('nan')); kv[:, :2 * D] = rnd(B * Nk, 2 * D)
+    heads = lambda t, n, c: t[:, c:c + D].reshape(B, n, H, hd).permute(0, 2, 1, 3).reshape(Z, n, hd).double()
+    Qr, Kr, Vr = heads(qkv, Nq, 0), heads(kv, Nk, 0), heads(kv, Nk, D)
+    qkv_d, kv_d = qkv.to(DEV, torch.bfloat16), kv.to(DEV, torch.bfloat16)
+    bh = dict(batch=Z, batch_inner=H)
+    f64 = lambda t: t.to(DEV).double()
+    # S = Q K^T: f32 [Z][Nq][Np], the Np - Nk padding columns not written
+    S = Guarded(Z * Nq, Nk, Np, torch.float32, DEV)
+    ops.gemm(qkv_d, kv_d, S.flat, Nq, Nk, hd, lda=ldq, ldb=ldkv, ldc=Np, a_off=0, b_off=0, c_off=S.off,
+             sA=(Nq * ldq, hd), sB=(Nk * ldkv, hd), sC=(H * Nq * Np, Nq * Np), **bh)
+    torch.cuda.synchronize()
+    S.intact('S')
+    ref = Qr @ Kr.transpose(1, 2)
+    bd = gamma(hd) * (Qr.abs() @ Kr.abs().transpose(1, 2))
+    assert_within(S.view.view(Z, Nq, Nk), f64(ref), f64(bd + ulp(torch.float32, ref.abs() + bd)), 'S', names=('z', 'q', 'k'))
+    # O = P V into the head columns of a packed [B * Nq][D] output (ld D + 8)
+    Pr = torch.zeros(Z, Nq, Np)
+    Pr[..., :Nk] = rnd(Z, Nq, Nk).abs()
+    Pr[..., Nk:] = 3.0
+    P_d = Pr.to(DEV, torch.bfloat16)
+    Pr = Pr[..., :Nk].double()
+    O = Guarded(B * Nq, D, D + 8, torch.bfloat16, DEV)
+    ops.gemm(P_d, kv_d, O.flat, Nq, hd, Nk, lda=Np, ldb=ldkv, ldc=O.ld, b_trans=True, b_off=D, c_off=O.off,
+             sA=(H * Nq * Np, Nq * Np), sB=(Nk * ldkv, hd), sC=(Nq * O.ld, hd), **bh)
+    torch.cuda.synchronize()
+    O.intact('O')
+    ref = Pr @ Vr
+    bd = gamma(Nk) * (Pr @ Vr.abs())
+    unhead = lambda t, n: t.reshape(B, H, n, hd).permute(0, 2, 1, 3).reshape(B * n, D)
+    assert_within(O.view, f64(unhead(ref, Nq)), f64(unhead(bd + ulp(torch.bfloat16, ref.abs() + bd), Nq)), 'O')
+    # the same product for head 1 alone (batch = B, batch_inner = 1): the other heads' columns are outside the view and stay untouched
+    O1 = Guarded(B * Nq, hd, D + 8, torch.bfloat16, DEV)
+    ops.gemm(P_d, kv_d, O1.flat, Nq, hd, Nk, lda=Np, ldb=ldkv, ldc=O1.ld, b_trans=True, a_off=Nq * Np, b_off=D + hd, c_off=O1.off,
+             batch=B, batch_inner=1, sA=(H * Nq * Np, 0), sB=(Nk * ldkv, 0), sC=(Nq * O1.ld, 0))
+    torch.cuda.synchronize()
+    O1.intact('single-head O')
+    assert torch.equal(O1.view, O.view[:, hd:2 * hd])
+    # dV = P^T dO (A k-strided: P's padding columns are rows past M of the product) and dK = dS^T Q into packed dk | dv
+    dO = torch.full((B * Nq, D + 8), float('nan')); dO[:, :D] = rnd(B * Nq, D)
+    dOr = dO[:, :D].reshape(B, Nq, H, hd).permute(0, 2, 1, 3).reshape(Z, Nq, hd).double()
+    dO_d = dO.to(DEV, torch.bfloat16)
+    dS = torch.zeros(Z, Nq, Np); dS[..., :Nk] = rnd(Z, Nq, Nk); dS[..., Nk:] = -7.0
+    dS_d = dS.to(DEV, torch.bfloat16)
+    dSr = dS[..., :Nk].double()
+    dKV = Guarded(B * Nk, 2 * D, 2 * D + 8, torch.bfloat16, DEV)
+    sP = (H * Nq * Np, Nq * Np)
+    ops.gemm(P_d, dO_d, dKV.flat, Nk, hd, Nq, lda=Np, ldb=D + 8, ldc=dKV.ld, a_trans=True, b_trans=True, c_off=dKV.off + D,
+             sA=sP, sB=(Nq * (D + 8), hd), sC=(Nk * dKV.ld, hd), **bh)
+    ops.gemm(dS_d, qkv_d, dKV.flat, Nk, hd, Nq, lda=Np, ldb=ldq, ldc=dKV.ld, a_trans=True, b_trans=True, c_off=dKV.off,
+             sA=sP, sB=(Nq * ldq, hd), sC=(Nk * dKV.ld, hd), **bh)
+    torch.cuda.synchronize()
+    dKV.intact('dk | dv')
+    for name, c, ref, bd in (('dk', 0, dSr.transpose(1, 2) @ Qr, dSr.abs().transpose(1, 2) @ Qr.abs()),
+                             ('dv', D, Pr.transpose(1, 2) @ dOr, Pr.transpose(1, 2) @ dOr.abs())):
+        bd = gamma(Nq) * bd
+        assert_within(dKV.view[:, c:c + D], f64(unhead(ref, Nk)), f64(unhead(bd + ulp(torch.bfloat16, ref.abs() + bd), Nk)), name)
 
 
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32])
@@ -134,6 +282,12 @@ def test_gemm_splitk_workspace(dtype):
     dw3 = torch.empty((N, K), device=DEV)
     ops.linear_dw(dyd, xd, dw3, accumulate=False)
     assert rel_err(dw2, ref) < 2e-6 and torch.equal(dw2, dw3)
+    # per element: any order of the Mr-term sums (split-K slabs and their fixed-order reduction included) stays within gamma_Mr;
+    # the accumulate adds 2.0 (gamma_(Mr + 1))
+    absp = dy.abs().t().double().to(DEV), x.abs().t().double().to(DEV)
+    assert_within(dw2, ref.to(DEV), prod_bound(*absp, Mr, torch.float32, ref.to(DEV)), 'split-K dW', names=('n', 'k'))
+    assert_within(dw, 2.0 + ref.to(DEV), prod_bound(*absp, Mr + 1, torch.float32, 2.0 + ref.to(DEV), extra=2.0 * gamma(Mr + 1)),
+                  'split-K dW accumulate', names=('n', 'k'))
 
 
 @pytest.mark.parametrize('Mr,N,K', [(12544, 1024, 256), (5000, 256, 136), (50176, 256, 256), (3000, 384, 264)])
@@ -218,6 +372,55 @@ def test_gemm_epilogues(dtype):
     c16 = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     ops.gemm(xd, wd, c16, M, N, K, lda=K, ldb=K, ldc=N, alpha=0.5)
     assert rel_err(c16.float(), 0.5 * (x @ w.t())) < 4e-3
+    _epilogues_per_element(dtype, x, w, bias, resid, dy, pre, gpre, out, aux, act, dxo, cs, aux_g, dxm, csm, dw, c16)
+
+
+# The bf16 epilogues' GELU pair (common.h gelu_both_fast4), as DESIGN.md section 6 item 12 states it from tools/gelu_poly_fit.py's fp32
+# emulation over |x| <= 20: |Phi error| 6.6e-6 on |x| <= 4 (|gelu error| <= 4 x 6.6e-6 there), gelu(-4) = -1.27e-4 held below -4,
+# relative 2.6e-5 above 4; GELU' within 5.5e-4 of the true derivative everywhere.  (f32 outputs use the exact erf form: inside these.)
+GELU_ABS, GELU_REL, DGELU_ABS = 1.3e-4, 2.6e-5, 5.5e-4
+# how an error in the pre-activation propagates: max |gelu'| = 1.129 (at x = 1.41), max |gelu''| = 2 phi(0) = 0.798
+GELU_D1, GELU_D2 = 1.13, 0.8
+
+
+def _epilogues_per_element(dtype, x, w, bias, resid, dy, pre, gpre, out, aux, act, dxo, cs, aux_g, dxm, csm, dw, c16):
+    """test_gemm_epilogues' outputs element by element against fp64.  u = 2^-24.  The product's error is prod_bound's gamma_K term;
+    each fp32 add / multiply of the epilogue adds u of its result; each 16-bit store one ulp; column sums over M rows add gamma_M."""
+    u = 2.0 ** -24
+    D = lambda t: t.double().to(DEV)
+    x, w, bias, resid, dy, pre, gpre = (D(t) for t in (x, w, bias, resid, dy, pre, gpre))
+    M, K = x.shape
+    N = w.shape[0]
+    Phi = lambda z: 0.5 * (1 + torch.erf(z / math.sqrt(2)))
+    phi = lambda z: torch.exp(-0.5 * z * z) / math.sqrt(2 * math.pi)
+    lin = x @ w.t() + bias
+    E_lin = prod_bound(x.abs(), w.abs(), K) + 2 * u * lin.abs()
+    r = lin + resid
+    assert_within(out, r, E_lin + 2 * u * r.abs() + ulp(torch.float32, r), 'bias + residual', names=('m', 'n'))
+    assert_within(aux, lin, E_lin + ulp(dtype, lin.abs() + E_lin), 'GELU aux (pre-activation)', names=('m', 'n'))
+    ge = lin * Phi(lin)
+    b = GELU_D1 * E_lin + GELU_ABS + GELU_REL * lin.abs()
+    assert_within(act, ge, b + ulp(dtype, ge.abs() + b), 'GELU', names=('m', 'n'))
+    dg = Phi(lin) + lin * phi(lin)
+    b = GELU_D2 * E_lin + DGELU_ABS
+    assert_within(aux_g, dg, b + ulp(dtype, dg.abs() + b), "GELU_G aux (gelu')", names=('m', 'n'))
+    g = dy @ w
+    Eg = prod_bound(dy.abs(), w.t().abs(), N)
+    d = Phi(pre) + pre * phi(pre)
+    r = g * d
+    b = GELU_D1 * Eg + g.abs() * DGELU_ABS + 2 * u * r.abs()
+    b = b + ulp(dtype, r.abs() + b)
+    assert_within(dxo, r, b, 'dGELU', names=('m', 'k'))
+    assert_within(cs, r.sum(0), b.sum(0) + gamma(M) * r.abs().sum(0), 'dGELU column sums')
+    r = g * gpre
+    b = Eg * gpre.abs() + 2 * u * r.abs()
+    b = b + ulp(dtype, r.abs() + b)
+    assert_within(dxm, r, b, 'MUL', names=('m', 'k'))
+    assert_within(csm, r.sum(0), b.sum(0) + gamma(M) * r.abs().sum(0), 'MUL column sums')
+    r = 1.0 + dy.t() @ x
+    assert_within(dw, r, prod_bound(dy.t().abs(), x.t().abs(), M + 1, torch.float32, r, extra=gamma(M + 1)), 'dW accumulate', names=('n', 'k'))
+    r = 0.5 * (x @ w.t())
+    assert_within(c16, r, prod_bound(0.5 * x.abs(), w.abs(), K, torch.bfloat16, r), 'alpha -> bf16', names=('m', 'n'))
 
 
 @pytest.mark.parametrize('shape', [(25344, 3072, 64), (25344, 2304, 96), (50176, 1024, 256)])
@@ -443,10 +646,224 @@ def _attention_case(dtype, geom, path):
     assert rel_err(dq.float().view(B, Nq, D), qr.grad) < tol
     assert rel_err(dkv.float().view(B, Nk, 2 * D)[..., :D], kr.grad) < tol
     assert rel_err(dkv.float().view(B, Nk, 2 * D)[..., D:], vr.grad) < tol
+    # and element by element (helpers.attention_bounds with this path's rounding points)
+    hv = lambda t, n: _heads(t, B, n, H, hd)
+    outs = dict(o=hv(od, Nq), dq=hv(dq, Nq), dk=hv(dkv[:, :D], Nk), dv=hv(dkv[:, D:], Nk))
+    flat = lambda t, n: t.reshape(B * n, D)
+    _check_attention(path, B, H, Nq, Nk, hd, flat(q, Nq), flat(k, Nk), flat(v, Nk), flat(do, Nq), outs, P[1] if P[0] == 'fused' else None,
+                     f'{path} {geom}')
 
 
 # ----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('D', [64, 128, 192, 256, 768, 1024])
+# Attention, element by element.  Per path: the product rounding u_in and the rounding of P / dS before their products (u_p), see
+# helpers.attention_bounds; the output type is the activation type.
+U_F16 = 2.0 ** -10 + 2.0 ** -20          # fp16 operands: two roundings of 2^-11 each per product (+ their 2^-22 cross term)
+_ATTN_ROUNDING = {'fused': (0.0, 2.0 ** -8), 'gemm': (0.0, 2.0 ** -8), 'f32': (0.0, 2.0 ** -24), 'f32x3': (U_X3, U_X3),
+                  'f32f16': (U_F16, 2.0 ** -11)}
+
+
+def _heads(t, B, N, H, hd):
+    """[B * N][>= H * hd] rows -> [B * H][N][hd]"""
+    return t[:, :H * hd].reshape(B, N, H, hd).permute(0, 2, 1, 3).reshape(B * H, N, hd)
+
+
+def _check_attention(path, B, H, Nq, Nk, hd, q, k, v, do, outs, lse, what):
+    """outs: dict of o / dq / dk / dv as [B * H][N][hd] device tensors (any of them), lse [B][H][Nq] or None"""
+    u_in, u_p = _ATTN_ROUNDING[path]
+    dt = torch.float32 if path in ('f32', 'f32x3', 'f32f16') else torch.bfloat16
+    f = lambda t, n: _heads(t.to(DEV), B, n, H, hd)
+    # fp16 P / dS: the subnormal floor 2^-25; dS is rounded in the units of dO pre-scaled by 2^-floor(log2 amax), i.e. 2^-25 amax in ours
+    eta = dict(eta_p=2.0 ** -25, eta_ds=2.0 ** -25 * float(do.abs().max())) if path == 'f32f16' else {}
+    r = attention_bounds(f(q, Nq), f(k, Nk), f(v, Nk), f(do, Nq), hd ** -0.5, u_in=u_in, u_p=u_p, out_dtype=dt, **eta)
+    for name, got in outs.items():
+        ref, bd = r[name]
+        assert_within(got, ref, bd, f'{what}: {name}', names=('bh', 'row', 'd'))
+    if lse is not None:
+        ref, bd = r['lse']
+        assert_within(lse.reshape(B * H, Nq), ref, bd, f'{what}: lse', names=('bh', 'q'))
+
+
+def _attention_packed(path, B, H, Nq, Nk, hd, q, k, v, do, extra=16):
+    """q, k, v, do: [B * N][D] float.  Runs the path's forward and backward the way the engine lays them out -- q inside a packed qkv
+    [B * Nq][3 D + extra] (k, v of the self-attention beside it), k | v inside a packed kv [B * Nk][2 D + extra], the extra columns NaN --
+    with out, dq and the packed dk | dv in guarded buffers.  Returns ({o, dq, dk, dv} as [B * H][N][hd], lse or None)."""
+    from multimae_amd import ops
+    from multimae_amd.ops import AttnView
+    D = H * hd
+    dt = torch.float32 if path in ('f32', 'f32x3', 'f32f16') else torch.bfloat16
+    f16 = path == 'f32f16'
+    qkv = torch.full((B * Nq, 3 * D + extra), float('nan'))
+    qkv[:, :D] = q
+    qkv[:, D:3 * D] = torch.randn(B * Nq, 2 * D)
+    kv = torch.full((B * Nk, 2 * D + extra), float('nan'))
+    kv[:, :D], kv[:, D:2 * D] = k, v
+    qkv_d, kv_d = qkv.to(DEV, dt), kv.to(DEV, dt)
+    O = Guarded(B * Nq, D, D + 8, dt, DEV)
+    dO = torch.full((B * Nq, D + 8), float('nan')); dO[:, :D] = do
+    dO_d = dO.to(DEV, dt)
+    ops.set_fused_attention(path in ('fused', 'f32x3', 'f32f16'))
+    try:
+        with ops.f32_gemm_mode('x3' if path in ('f32x3', 'f32f16') else 'exact'):
+            st = ops.attention_fwd(AttnView(qkv_d, 0, qkv.shape[1], Nq), AttnView(kv_d, 0, kv.shape[1], Nk), AttnView(kv_d, D, kv.shape[1], Nk),
+                                   AttnView(O.full, 0, O.ld, Nq), B, H, hd, hd ** -0.5, f16=f16)
+            fused = ops._fusable(AttnView(qkv_d, 0, 1, Nq), AttnView(kv_d, 0, 1, Nk), hd)
+            dOv = AttnView(dO_d, 0, D + 8, Nq)                      # (dO shares o's row stride, as the fused backward requires)
+            dQ = Guarded(B * Nq, D, D + 8, dt, DEV)
+            dKV = Guarded(B * Nk, 2 * D, 2 * D + 8, dt, DEV)
+            amax = do.abs().max().reshape(1).to(DEV) if f16 else None
+            ops.attention_bwd(AttnView(qkv_d, 0, qkv.shape[1], Nq), AttnView(kv_d, 0, kv.shape[1], Nk), AttnView(kv_d, D, kv.shape[1], Nk), st,
+                              AttnView(O.full, 0, O.ld, Nq), dOv, AttnView(dQ.full, 0, dQ.ld, Nq), AttnView(dKV.full, 0, dKV.ld, Nk),
+                              AttnView(dKV.full, D, dKV.ld, Nk), B, H, hd, hd ** -0.5, f16=f16, dy_amax=amax)
+    finally:
+        ops.set_fused_attention(True)
+    torch.cuda.synchronize()
+    assert st[0] == ('fused' if fused else 'gemm') and (fused or path in ('gemm', 'f32', 'f32x3')), (st[0], path)
+    for g, name in ((O, 'o'), (dQ, 'dq'), (dKV, 'dk | dv')):
+        g.intact(f'{path} {B}x{H}x{Nq}x{Nk}x{hd}: {name}')
+    outs = dict(o=_heads(O.view, B, Nq, H, hd), dq=_heads(dQ.view, B, Nq, H, hd), dk=_heads(dKV.view[:, :D], B, Nk, H, hd),
+                dv=_heads(dKV.view[:, D:], B, Nk, H, hd))
+    return outs, (st[1] if st[0] == 'fused' else None)
+
+
+_ATTN_GEOMS = [(2, 2, 1, 33, 32), (1, 3, 31, 32, 64), (2, 2, 33, 1, 64), (1, 2, 64, 65, 32), (2, 2, 65, 31, 64), (1, 2, 196, 197, 32),
+               (1, 2, 197, 196, 64), (1, 1, 255, 256, 32), (1, 2, 256, 255, 64), (1, 1, 32, 256, 64), (1, 1, 256, 33, 32)]
+
+
+def _attn_fits(path, Nq, Nk, hd):
+    """f32f16 has no GEMM fallback in ops: only geometries whose backward tiles fit the LDS"""
+    r = lambda n: (n + 31) // 32 * 32
+    return path != 'f32f16' or 4 * (r(Nq) + r(Nk)) * hd * 2 + 8 * r(Nq) <= 160 * 1024
+
+
+@pytest.mark.parametrize('path', ['fused', 'gemm', 'f32', 'f32x3', 'f32f16'])
+def test_attention_one_hot_probe(path):
+    """Each query row's scores have a margin of 30 at one chosen key (key 0, 31, 32, 33 and the last key of a ragged tail, in turn):
+    o must be that key's v row -- bit for bit in bf16, to one ulp in f32 -- lse the fp64 logsumexp, and with a one-hot dO, dv lands on
+    exactly the chosen rows (every other row gets e^-30 of it).  Nq, Nk across the 32-wide tile edges, both head widths, packed
+    inputs with NaN columns beside them, guarded outputs."""
+    for B, H, Nq, Nk, hd in _ATTN_GEOMS:
+        if not _attn_fits(path, Nq, Nk, hd):
+            continue
+        D, sc = H * hd, hd ** -0.5
+        g = torch.Generator().manual_seed(Nq * 1000 + Nk)
+        chosen = sorted({c for c in (0, 31, 32, 33, Nk - 1) if c < Nk})
+        a = 8.0
+        b = 30.0 / (a * sc)
+        k = torch.zeros(B * Nk, H, hd)
+        k[..., 8:] = bf(torch.randn(B * Nk, H, hd - 8, generator=g) * 0.5).float()
+        kr = k.view(B, Nk, H, hd)
+        for i, c in enumerate(chosen):
+            kr[:, c, :, i] = a                                            # key c alone has a component on dimension i
+        pick = torch.tensor(chosen)[torch.arange(Nq) % len(chosen)]      # query row r selects key pick[r]
+        q = torch.zeros(B, Nq, H, hd)
+        q[:, torch.arange(Nq), :, (torch.arange(Nq) % len(chosen))] = bf(torch.tensor(b)).float()
+        v = torch.randn(B * Nk, D, generator=g).sign() * (1 + torch.rand(B * Nk, D, generator=g))
+        v = bf(v).float()                                                 # |v| in [1, 2]: bf16 values, exact in fp16 too
+        do = torch.zeros(B, Nq, H, hd)
+        do[:, :, :, 0] = bf(torch.randn(B, Nq, H, generator=g)).float()
+        q, k, do = q.reshape(B * Nq, D), k.reshape(B * Nk, D), do.reshape(B * Nq, D)
+        if path == 'f32f16':
+            do = do * 2.0 ** -20                                          # (the amax pre-scale brings it back into fp16's range)
+        outs, lse = _attention_packed(path, B, H, Nq, Nk, hd, q, k, v, do)
+        what = f'{path} one-hot {B}x{H}x{Nq}x{Nk}x{hd}'
+        want = _heads(v.to(DEV), B, Nk, H, hd)[:, pick.to(DEV)]         # [B * H][Nq][hd]: the chosen key's v row
+        if path in ('fused', 'gemm'):
+            assert_within(outs['o'], want, 0.0, what + ': o', names=('bh', 'q', 'd'))
+        else:
+            assert_within(outs['o'], want, ulp(torch.float32, want), what + ': o', names=('bh', 'q', 'd'))
+        # dv on exactly the chosen rows (the others get e^-30 of a dO row: inside the bound's ulp of ~1e-13), dq, dk, lse per element
+        _check_attention(path, B, H, Nq, Nk, hd, q, k, v, do, {'dv': outs['dv'], 'dq': outs['dq'], 'dk': outs['dk']}, lse, what)
+
+
+@pytest.mark.parametrize('path', ['fused', 'gemm', 'f32', 'f32x3', 'f32f16'])
+def test_attention_packed_guarded_per_element(path):
+    """Random operands with peaky scores (q and k x2), every geometry of _ATTN_GEOMS: o, lse (fused kernels), dq, dk and dv within the
+    per-element bounds of helpers.attention_bounds, packed inputs with NaN columns beside them, guarded outputs."""
+    for B, H, Nq, Nk, hd in _ATTN_GEOMS:
+        if not _attn_fits(path, Nq, Nk, hd):
+            continue
+        D = H * hd
+        g = torch.Generator().manual_seed(Nq * 7 + Nk)
+        q, k = (torch.randn(B * n, D, generator=g) * 2 for n in (Nq, Nk))
+        v, do = torch.randn(B * Nk, D, generator=g), torch.randn(B * Nq, D, generator=g)
+        if path == 'f32f16':
+            do = do * 2.3e-8
+        if path in ('fused', 'gemm'):
+            q, k, v, do = (bf(t).float() for t in (q, k, v, do))
+        outs, lse = _attention_packed(path, B, H, Nq, Nk, hd, q, k, v, do)
+        _check_attention(path, B, H, Nq, Nk, hd, q, k, v, do, outs, lse, f'{path} {B}x{H}x{Nq}x{Nk}x{hd}')
+
+
+@pytest.mark.parametrize('hd', [32, 64])
+def test_attention_raw_abi_batch_gap_rows(hd):
+    """mmae_attn_fwd / mmae_attn_bwd called directly with batch strides larger than N x row stride: NaN rows between the batches of
+    q, k, v, o and dO.  Tail rows of the 32-wide tiles must be zero-filled, not read (a NaN times P = 0 is NaN); the outputs' gap rows
+    stay untouched."""
+    from multimae_amd import _lib, ops
+    lib = _lib.load()
+    B, H, Nq, Nk, gap = 2, 2, 45, 70, 5
+    D, ld = H * hd, H * hd + 8
+    g = torch.Generator().manual_seed(hd)
+
+    def gapped(N, vals):
+        t = torch.full((B, N + gap, ld), float('nan'))
+        t[:, :N, :D] = vals.view(B, N, D)
+        return t.reshape(B * (N + gap), ld).to(DEV, torch.bfloat16)
+
+    q, k, v, do = (bf(torch.randn(B * n, D, generator=g) * s).float() for n, s in ((Nq, 2), (Nk, 2), (Nk, 1), (Nq, 1)))
+    qd, kd, vd, dod = gapped(Nq, q), gapped(Nk, k), gapped(Nk, v), gapped(Nq, do)
+    sbq, sbk = (Nq + gap) * ld, (Nk + gap) * ld
+    O, dQ = Guarded(B * (Nq + gap), D, ld, torch.bfloat16, DEV), Guarded(B * (Nq + gap), D, ld, torch.bfloat16, DEV)
+    dK, dV = Guarded(B * (Nk + gap), D, ld, torch.bfloat16, DEV), Guarded(B * (Nk + gap), D, ld, torch.bfloat16, DEV)
+    lse = torch.full((B, H, Nq), float('nan'), device=DEV)
+    sc = hd ** -0.5
+    _lib.check(lib.mmae_attn_fwd(qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), O.full.data_ptr(), lse.data_ptr(), B, H, Nq, Nk, hd,
+                                 sbq, ld, sbk, ld, sbk, ld, sbq, ld, sc, ops._stream()), 'attn_fwd')
+    _lib.check(lib.mmae_attn_bwd(qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), O.full.data_ptr(), dod.data_ptr(), lse.data_ptr(), dQ.full.data_ptr(),
+                                 dK.full.data_ptr(), dV.full.data_ptr(), B, H, Nq, Nk, hd, sbq, ld, sbk, ld, sbk, ld, sbq, ld, sbq, ld, sbk, ld,
+                                 sbk, ld, sc, ops._stream()), 'attn_bwd')
+    torch.cuda.synchronize()
+    rows = lambda G, N: G.view.view(B, N + gap, D)
+    for G, N, name in ((O, Nq, 'o'), (dQ, Nq, 'dq'), (dK, Nk, 'dk'), (dV, Nk, 'dv')):
+        G.intact(name)
+        assert bool((rows(G, N)[:, N:].contiguous().view(torch.int16) == -91).all()), f'{name}: a gap row between batches was written'
+    dense = lambda G, N: rows(G, N)[:, :N].reshape(B * N, D)
+    outs = {name: _heads(dense(G, N), B, N, H, hd) for G, N, name in ((O, Nq, 'o'), (dQ, Nq, 'dq'), (dK, Nk, 'dk'), (dV, Nk, 'dv'))}
+    _check_attention('fused', B, H, Nq, Nk, hd, q, k, v, do, outs, lse, f'raw ABI gap rows hd {hd}')
+
+
+def test_attention_fp16_storage_one_hot_probe():
+    """mmae_attn_fwd_f16 (fp16 tensors in memory): the one-hot probe -- o bit-equal to the chosen key's v row, lse the fp64 logsumexp."""
+    from multimae_amd import _lib, ops
+    lib = _lib.load()
+    for B, H, Nq, Nk, hd in ((2, 2, 33, 65, 32), (1, 2, 197, 256, 64)):
+        D, sc = H * hd, hd ** -0.5
+        chosen = sorted({c for c in (0, 31, 32, 33, Nk - 1) if c < Nk})
+        k = torch.zeros(B, Nk, H, hd)
+        k[..., 8:] = torch.randn(B, Nk, H, hd - 8).half().float() * 0.5
+        for i, c in enumerate(chosen):
+            k[:, c, :, i] = 8.0
+        q = torch.zeros(B, Nq, H, hd)
+        q[:, torch.arange(Nq), :, torch.arange(Nq) % len(chosen)] = 30.0 / (8.0 * sc)
+        q = q.half().float()
+        pick = torch.tensor(chosen)[torch.arange(Nq) % len(chosen)]
+        v = (torch.randn(B, Nk, D).sign() * (1 + torch.rand(B, Nk, D))).half().float()
+        qd, kd, vd = (t.reshape(B * t.shape[1], D).to(DEV, torch.float16) for t in (q, k, v))
+        O = Guarded(B * Nq, D, D + 8, torch.float16, DEV)
+        lse = torch.empty((B, H, Nq), device=DEV)
+        _lib.check(lib.mmae_attn_fwd_f16(qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), O.full.data_ptr(), lse.data_ptr(), B, H, Nq, Nk, hd,
+                                         Nq * D, D, Nk * D, D, Nk * D, D, Nq * O.ld, O.ld, sc, ops._stream()), 'attn_fwd_f16')
+        torch.cuda.synchronize()
+        O.intact('f16 o')
+        want = _heads(v.reshape(B * Nk, D).to(DEV), B, Nk, H, hd)[:, pick.to(DEV)]
+        assert_within(_heads(O.view, B, Nq, H, hd), want, 0.0, 'f16 one-hot o', names=('bh', 'q', 'd'))
+        s = sc * (_heads(q.reshape(B * Nq, D), B, Nq, H, hd).double() @ _heads(k.reshape(B * Nk, D), B, Nk, H, hd).double().transpose(1, 2))
+        ref = torch.logsumexp(s, -1).to(DEV)
+        assert_within(lse.reshape(B * H, Nq), ref, gamma(hd) * 30 + gamma(Nk) + 8 * ulp(torch.float32, ref.abs() + 1), 'f16 one-hot lse')
+
+
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('D', [4, 12, 36, 64, 100, 128, 192, 256, 384, 516, 768, 1020, 1024])
 def test_layernorm_fwd_bwd(D):
     from multimae_amd import ops
     torch.manual_seed(3)
@@ -468,6 +885,70 @@ def test_layernorm_fwd_bwd(D):
     assert rel_err(dg, wr.grad) < 1e-5 and rel_err(db, br.grad) < 1e-5
     dx2, none, _, _, _ = ops.layernorm_bwd(bf(dy).to(DEV), x.to(DEV), w.to(DEV), mean, rstd, None, None)
     assert none is None and rel_err(dx2, xr.grad) < 6e-3
+    _layernorm_per_element(D, x, w, b, dy, dxin, y, y16, mean, rstd, dx, dxa, dg, db, cs, dx2)
+
+
+def _layernorm_per_element(D, x, w, b, dy, dxin, y, y16, mean, rstd, dx, dxa, dg, db, cs, dx2):
+    """test_layernorm_fwd_bwd's outputs against fp64, element by element (row statistics per row).  u = 2^-24; the kernel works in fp32:
+      mean    |dm| <= gamma_D mean|x| + ulp                                      (a sum of D terms, / D)
+      rstd    relative rho <= gamma_(2D+4) mean(x^2) / var / 2 + 2^-21             (variance by either one- or two-pass sums, halved by the
+                                                                                    square root; v_rsq_f32 within 1 ulp)
+      xhat    |dxh| <= |xh| (rho + 2u) + rstd |dm|
+      y       |dy_| <= |w| |dxh| + 4u (|xh w| + |b|) + ulp(out)
+      dx      = dx_in + rstd (g - mean g - xh mean(g xh)), g = dy w:
+              |ddx| <= rho |dx - dx_in| + rstd (gamma_D mean|g| + |dxh| mean|g xh| + |xh| mean(|g| |dxh|) + gamma_D |xh| mean|g xh|)
+                       + 6u (|dx_in| + rstd (|g| + mean|g| + |xh| mean|g xh|)) + ulp
+      sums    over R rows: the rows' bounds summed + gamma_R sum of magnitudes"""
+    u = 2.0 ** -24
+    xd, wd, bd_, dyd = x.double().to(DEV), w.double().to(DEV), b.double().to(DEV), dy.double().to(DEV)
+    dxi = dxin.double().to(DEV)
+    R = xd.shape[0]
+    m = xd.mean(1)
+    xc = xd - m[:, None]
+    var = (xc * xc).mean(1)
+    rs = 1.0 / torch.sqrt(var + 1e-6)
+    xh = xc * rs[:, None]
+    b_m = gamma(D) * xd.abs().mean(1) + ulp(torch.float32, m)
+    rho = gamma(2 * D + 4) * (xd * xd).mean(1) / var / 2 + 2.0 ** -21
+    assert_within(mean, m, b_m, 'mean')
+    assert_within(rstd, rs, rho * rs + ulp(torch.float32, rs), 'rstd')
+    e_xh = xh.abs() * (rho[:, None] + 2 * u) + rs[:, None] * b_m[:, None]
+    yr = xh * wd + bd_
+    b_y = wd.abs() * e_xh + 4 * u * ((xh * wd).abs() + bd_.abs())
+    assert_within(y, yr, b_y + ulp(torch.float32, yr.abs() + b_y), 'y f32', names=('row', 'col'))
+    assert_within(y16, yr, b_y + ulp(torch.bfloat16, yr.abs() + b_y), 'y bf16', names=('row', 'col'))
+
+    def dx_ref(dyv, dx_in):
+        g = dyv * wd
+        gx = (g * xh).mean(1, keepdim=True)
+        ref = dx_in + rs[:, None] * (g - g.mean(1, keepdim=True) - xh * gx)
+        bd = (rho[:, None] * (ref - dx_in).abs() + rs[:, None] * (gamma(D) * g.abs().mean(1, keepdim=True) + e_xh * (g * xh).abs().mean(1, keepdim=True)
+              + xh.abs() * (g.abs() * e_xh).mean(1, keepdim=True) + gamma(D) * xh.abs() * (g * xh).abs().mean(1, keepdim=True))
+              + 6 * u * (dx_in.abs() + rs[:, None] * (g.abs() + g.abs().mean(1, keepdim=True) + xh.abs() * (g * xh).abs().mean(1, keepdim=True))))
+        return ref, bd + ulp(torch.float32, ref.abs() + bd)
+
+    dxr, b_dx = dx_ref(dyd, dxi)
+    assert_within(dx, dxr, b_dx, 'dx', names=('row', 'col'))
+    assert_within(dxa, dxr, b_dx + ulp(torch.bfloat16, dxr.abs() + b_dx), 'dx_act', names=('row', 'col'))
+    assert_within(cs, dxr.sum(0), b_dx.sum(0) + gamma(R) * dxr.abs().sum(0), 'colsum(dx)')
+    assert_within(dg, (dyd * xh).sum(0), (dyd.abs() * e_xh).sum(0) + gamma(R + 1) * (dyd * xh).abs().sum(0), 'dgamma')
+    assert_within(db, dyd.sum(0), gamma(R) * dyd.abs().sum(0), 'dbeta')
+    dxr2, b_dx2 = dx_ref(bf(dy).double().to(DEV), torch.zeros_like(dxi))      # (dy given in bf16: the reference takes the rounded values)
+    assert_within(dx2, dxr2, b_dx2, 'dx, bf16 dy', names=('row', 'col'))
+
+
+@pytest.mark.parametrize('D', [1028, 6, 2])
+def test_layernorm_refuses_widths_it_does_not_support(D):
+    """mmae_layernorm_fwd takes multiples of 4 in [4, 1024]: anything else is MMAE_EINVAL, and the wrapper raises."""
+    from multimae_amd import _lib, ops
+    x = torch.randn(8, D, device=DEV)
+    with pytest.raises(_lib.KernelError, match=r'rc=-1\).*multiple of 4'):
+        ops.layernorm_fwd(x, torch.ones(D, device=DEV), torch.zeros(D, device=DEV), 1e-6, torch.float32)
+    MMAE_EINVAL = -1                                                         # include/mmae.h
+    assert _lib.load().mmae_layernorm_fwd(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), 0, x.data_ptr(), x.data_ptr(), 8, D, 1e-6,
+                                          ops._stream()) == MMAE_EINVAL
+
+
 
 
 def test_softmax_colsum_cast_transpose():
@@ -475,16 +956,33 @@ def test_softmax_colsum_cast_transpose():
     torch.manual_seed(4)
     rows, n, ld = 500, 99, 104
     S = torch.randn(rows, ld) * 3
-    P = torch.full((rows, ld), 7.0, device=DEV)
+    Pg = Guarded(rows, ld, ld, torch.float32, DEV, fill=torch.full((rows, ld), 7.0))     # (the wrapper passes ld = the last dimension)
+    P = Pg.view
     ops.softmax_fwd(S.to(DEV), P, rows, n, 0.125)
     ref = (S[:, :n] * 0.125).softmax(-1)
     assert rel_err(P[:, :n], ref) < 2e-6 and float(P[:, n:].abs().max()) == 0.0
+    # per element: scaled scores carry 2u (the scale multiply, log2 e folded in), the max-shifted exponent 2^-22 (v_exp_f32), the fp32 sum
+    # gamma_n: |dP| <= P (2 (2u |s|max) + gamma_n + 2^-21) + ulp
+    u = 2.0 ** -24
+    s64 = S[:, :n].double().to(DEV) * 0.125
+    p64 = torch.softmax(s64, -1)
+    bP = p64 * (4 * u * s64.abs().amax(1, keepdim=True) + gamma(n) + 2.0 ** -21)
+    assert_within(P[:, :n], p64, bP + ulp(torch.float32, p64), 'softmax P', names=('row', 'col'))
+    Pg.intact('softmax P')
     dP = torch.randn(rows, ld)
-    dS = torch.full((rows, ld), 7.0, device=DEV)
+    dSg = Guarded(rows, ld, ld, torch.float32, DEV, fill=torch.full((rows, ld), 7.0))
+    dS = dSg.view
     ops.softmax_bwd(P, dP.to(DEV), dS, rows, n, 0.125)
     sr = S[:, :n].clone().requires_grad_(True)
     (sr * 0.125).softmax(-1).backward(dP[:, :n])
     assert rel_err(dS[:, :n], sr.grad) < 5e-6 and float(dS[:, n:].abs().max()) == 0.0
+    # per element, from the kernel's own P: dS = scale P (dP - delta), delta = sum P dP in fp32 (gamma_n), then two products and a difference (3u)
+    Pk, dPd = P[:, :n].double(), dP[:, :n].double().to(DEV)
+    delta = (Pk * dPd).sum(1, keepdim=True)
+    dS64 = 0.125 * Pk * (dPd - delta)
+    bS = 0.125 * Pk * (3 * u * ((dPd - delta).abs() + delta.abs()) + gamma(n) * (Pk * dPd.abs()).sum(1, keepdim=True))
+    assert_within(dS[:, :n], dS64, bS + ulp(torch.float32, dS64.abs() + bS), 'softmax dS', names=('row', 'col'))
+    dSg.intact('softmax dS')
     # column sums
     for dt in (torch.float32, torch.bfloat16):
         dy = torch.randn(3001, 264)
@@ -492,11 +990,15 @@ def test_softmax_colsum_cast_transpose():
         out = torch.ones(264, device=DEV)
         ops.colsum(dyd, out, True)
         assert rel_err(out, 1.0 + dyd.float().cpu().sum(0)) < 1e-5
+        d64 = dyd.double()
+        ref = 1.0 + d64.sum(0)
+        assert_within(out, ref, gamma(3002) * (1.0 + d64.abs().sum(0)), f'colsum {dt}')       # 3001 rows + the accumulated 1
     # ragged widths (a 7-class head): the one-column-per-lane kernel
     dy = torch.randn(1003, 7).to(DEV)
     out = torch.zeros(7, device=DEV)
     ops.colsum(dy, out, False)
     assert rel_err(out, dy.double().sum(0).cpu()) < 1e-5
+    assert_within(out, dy.double().sum(0), gamma(1003) * dy.double().abs().sum(0), 'colsum, 7 columns')
     # scattered column sums: short/wide partial blocks (the LayerNorm / dGELU reductions), segments to separate
     # destinations, a dropped segment, accumulate on and off
     for M_, seg, nseg in ((512, 768, 3), (396, 3072, 1), (7, 64, 5), (25344, 256, 2)):
