@@ -588,7 +588,7 @@ int mmae_axpy_f32(float* y, const float* x, float a, int64_t n, void* stream);
 int mmae_add_n_f32(float* out, const float* const* in_host, int n_in, int64_t n, void* stream);
 /* stochastic depth (multimae_utils.py:105-122) on 2-D activations, rows grouped N per sample, s f32 [R/N]:
  *   rowscale_add:  out[r][:] = resid[r][:] + s[r / N] * y[r][:]                 (f32, out may alias resid)
- *   rowscale_cast: out[r][:] = cast(s[r / N] * x[r][:])   (x f32; out act dtype) */
+ *   rowscale_cast: out[r][:] = cast(s[r / N] * x[r][:])   (x f32; out MMAE_F32 / MMAE_BF16 / MMAE_F16, any other code is refused) */
 int mmae_rowscale_add(const float* resid, const float* y, const float* s, float* out, int64_t R, int N, int D, void* stream);
 int mmae_rowscale_cast(const float* x, const float* s, void* out, int out_dtype, int64_t R, int N, int D, void* stream);
 /* nn.Dropout (Mlp.drop, attn_drop, proj_drop: multimae_utils.py:138-155, 158-214; the mask itself is drawn by the caller) as ONE
@@ -745,7 +745,11 @@ int mmae_masked_pixel_loss_fwd(const float* pred, const float* target, const int
 int mmae_masked_pixel_loss_bwd(const float* pred, const float* target, const int64_t* mask, int kind, int norm_pix,
                                int B, int C, int H, int W, int patch, const float* stats, const float* per_sample,
                                const float* loss, const float* upstream, float* d_pred, void* stream);
-/* label_smoothing as F.cross_entropy's (criterion.py:47): (1 - eps) * nll(target) + eps * mean over classes of -log p_c */
+/* label_smoothing as F.cross_entropy's (criterion.py:47): (1 - eps) * nll(target) + eps * mean over classes of -log p_c.
+ * Targets outside [0, C) are ignored as F.cross_entropy ignores ignore_index = -100: zero loss and zero gradient at that pixel
+ * (the label-smoothing term included), the pixel still counts in per_sample's count, and the logits are never read at that
+ * index.  This holds for the four CE entry points (image and patch domain).  The reference raises for any other value outside
+ * [0, C) (e.g. 255 from u8 labels with C = 133); these kernels ignore it. */
 int mmae_masked_ce_fwd(const float* logits, const int64_t* target, const int64_t* mask, int B, int C, int H, int W,
                        int patch, float label_smoothing, float* lse, float* partial, float* per_sample, float* loss, void* stream);
 int mmae_masked_ce_bwd(const float* logits, const int64_t* target, const int64_t* mask, int B, int C, int H, int W,

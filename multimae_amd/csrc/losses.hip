@@ -154,7 +154,9 @@ __global__ void __launch_bounds__(256) ce_fwd_kernel(const float* __restrict__ l
         }
         const float ls = mx + logf(s);
         lse[(long long)b * HW + px] = ls;
-        const float nll = ls - l[target[(long long)b * HW + px] * HW];
+        const long long t = target[(long long)b * HW + px];
+        if (t < 0 || t >= C) continue;               // ignored target (mmae.h): no loss, the pixel still counts
+        const float nll = ls - l[t * HW];
         acc += eps == 0.f ? nll : (1.f - eps) * nll + eps * (ls - sx / (float)C);
     }
     float dummy = 0.f;
@@ -173,10 +175,11 @@ __global__ void ce_bwd_kernel(const float* __restrict__ logits, const long long*
     const int c = (int)(r % C); const long long b = r / C;
     const int y = px / W, x = px % W, nw = W / P, np = (H / P) * nw;
     float g = 0.f;
-    if (mask[b * np + (y / P) * nw + x / P] != 0) {
+    const long long t = target[b * HW + px];
+    if (mask[b * np + (y / P) * nw + x / P] != 0 && t >= 0 && t < C) {
         const float wgt = upstream[0] / (loss[1] * per_sample[b * 2 + 1]);
         const float sm = expf(logits[i] - lse[b * HW + px]);
-        g = wgt * (sm - ((target[b * HW + px] == c ? 1.f - eps : 0.f) + eps / (float)C));
+        g = wgt * (sm - ((t == c ? 1.f - eps : 0.f) + eps / (float)C));
     }
     d_logits[i] = g;
 }
@@ -227,7 +230,8 @@ __global__ void __launch_bounds__(256) ce_bwd4_kernel(const float* __restrict__ 
         const f32x4 lg = ld4(logits + i), ls = ld4(lse + b * HW + px);
         const long long* t = target + b * HW + px;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) g[j] = wgt * (expf(lg[j] - ls[j]) - ((t[j] == c ? 1.f - eps : 0.f) + eps / (float)C));
+        for (int j = 0; j < 4; ++j)
+            if (t[j] >= 0 && t[j] < C) g[j] = wgt * (expf(lg[j] - ls[j]) - ((t[j] == c ? 1.f - eps : 0.f) + eps / (float)C));
     }
     st4(d_logits + i, g);
 }
@@ -438,7 +442,9 @@ __global__ void __launch_bounds__(256) ce_pat_fwd_kernel(const float* __restrict
         }
         const float ls = mx + logf(s);
         if (slot == 0) { lse_pat[row * npix + pix] = ls; }
-        float contrib = slot == 0 ? (eps == 0.f ? ls - lt : (1.f - eps) * (ls - lt) + eps * (ls - sx / (float)C)) : 0.f;
+        // an ignored target (outside [0, C), mmae.h) adds nothing; its pixel still counts
+        const bool tok = t >= 0 && t < C;
+        float contrib = slot == 0 && tok ? (eps == 0.f ? ls - lt : (1.f - eps) * (ls - lt) + eps * (ls - sx / (float)C)) : 0.f;
         contrib = wave_sum(contrib);
         if (lane == 0) acc += contrib;
     }
@@ -487,6 +493,7 @@ __global__ void __launch_bounds__(256) ce_pat_bwd_kernel(const float* __restrict
     const float wgt = gs * upstream[0] / (loss[1] * per_sample[b * 2 + 1]);
     const float ls = lse_pat[row * npix + pix];
     const long long t = target[((long long)b * H + py * P + pix / P) * W + px * P + pix % P];
+    const bool tok = t >= 0 && t < C;                // ignored target (mmae.h): zero gradient
     const float* prow = pat + row * nval;
     float gmax = 0.f;
     // four independent loads in flight per lane (one per iteration left the kernel at 22 VGPRs and latency-bound: 3.5 TB/s)
@@ -500,7 +507,7 @@ __global__ void __launch_bounds__(256) ce_pat_bwd_kernel(const float* __restrict
             if (e < (int)ld) {
                 const int c = slot + (e >> 6) * nslot;
                 float g = 0.f;
-                if (e < nval) g = wgt * (expf(v[k] - ls) - (((long long)c == t ? 1.f - eps : 0.f) + eps / (float)C));
+                if (e < nval && tok) g = wgt * (expf(v[k] - ls) - (((long long)c == t ? 1.f - eps : 0.f) + eps / (float)C));
                 gmax = fmaxf(gmax, fabsf(g));
                 ActT<DT>::st(drow + e, g);
             }

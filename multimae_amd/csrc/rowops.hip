@@ -927,7 +927,10 @@ int mmae_rowscale_cast(const float* x, const float* s, void* out, int out_dtype,
     MMAE_REQUIRE(x && s && out && R > 0 && N > 0 && D > 0 && D % 4 == 0 && R % N == 0, "rowscale_cast: bad argument");
     MMAE_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0), "rowscale_cast: unaligned");
     const long long total4 = (long long)R * (D / 4);
+    // every other dtype code used to take the f32 path and write 4-byte values into a 16-bit buffer
+    MMAE_REQUIRE(out_dtype == MMAE_F32 || out_dtype == MMAE_BF16 || out_dtype == MMAE_F16, "rowscale_cast: out_dtype must be f32, bf16 or fp16");
     if (out_dtype == MMAE_BF16) hipLaunchKernelGGL((rowscale_cast_kernel<uint16_t>), dim3(stream_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, s, (uint16_t*)out, total4, D / 4, N);
+    else if (out_dtype == MMAE_F16) hipLaunchKernelGGL((rowscale_cast_kernel<h16_t>), dim3(stream_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, s, (h16_t*)out, total4, D / 4, N);
     else hipLaunchKernelGGL((rowscale_cast_kernel<float>), dim3(stream_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, s, (float*)out, total4, D / 4, N);
     return mmae_check_launch("rowscale_cast");
 }

@@ -282,3 +282,143 @@ def attention_bounds(q, k, v, do, scale: float, *, u_in: float, u_p: float, out_
     b_dk = b_dk + ulp(grad_dtype, dk.abs() + b_dk)
     b_dv = b_dv + ulp(grad_dtype, dv.abs() + b_dv)
     return dict(o=(o, b_o), lse=(lse, b_lse), dq=(dq, b_dq), dk=(dk, b_dk), dv=(dv, b_dv), P=P)
+
+
+# ----------------------------------------------------------------------------------------------
+# Masked losses (losses.hip): fp64 references with element-wise bounds, shared by the image- and patch-domain tests and the helper
+# self-tests.  The kernels' rounding points, u = 2^-24, device expf / logf taken as <= 1 ulp (<= 2u relative):
+#   counts     exact (integers below 2^24)
+#   norm_pix   mu = fp32 sum / nval:              |dmu| <= (gamma_nval + u) mean|t| = e_mu
+#              var = fp32 sum of (t - mu^)^2 / (nval - 1): |dvar| <= (gamma_nval + 4u)(var + k e_mu^2) + k e_mu^2 + u 1e-6,
+#              k = nval / (nval - 1) (the shift by mu^ - mu adds k dmu^2; the fp32 constant 1e-6f is 1e-6 within u)
+#              rs = 1 / sqrtf(var + 1e-6):       |drs| / rs <= 0.51 |dvar| / (var + 1e-6) + 3u = r_rs   (first order, 2 % slack)
+#   residual   d = p - (t - mu^) rs^:            |dd| <= e_mu rs (1 + r_rs) + |t - mu| rs (r_rs + 2u) + u (|d| + that)  (u |d| alone
+#              without norm_pix)
+#   error      MSE: |d^2 - d^^2| <= 2 |d| dd + dd^2 + u d^2;  L1: dd
+#   sums       fp32 over the n masked elements of a sample, the split partials and the /C:  + (gamma_(n + 16) + u) sum|e|
+#   loss       sum_b s_b / c_b (fp32), / nvalid:  sum_b ds_b / c_b + (gamma_(B + 8) + 2u) sum_b s_b / c_b, / nvalid
+#   weight     w_b = up / (nvalid c_b C) in fp32 (two products and a division): |dw| <= 4u |w|
+#   gradient   MSE: g = w 2 d:  |dg| <= 2 |w| dd + 6u |g|;  L1: g = w sign(d^) -- exact unless |d| <= dd, then any of {-w, 0, +w}
+#   CE lse     online max + rescaled fp32 sum of C exps, each exp's argument rounded (u |v - mx| <= u range, the rescales' arguments
+#              add up to at most the range), every rescale one more expf and product (3u; n_r rescales: the records of the running maximum
+#              in the image domain, the lane's groups of eight plus two per slot combination on patch rows):
+#              |ds| / s <= gamma_(C + 8) + 2u + 3u n_r + 4u range = r_s;  lse = mx + logf(s): |dlse| <= 1.01 r_s + 2u |log s| + u |lse|
+#   CE nll     ls - l_t (+ eps (ls - sx / C), sx an fp32 sum of C logits):  per pixel
+#              (1 - eps)(dlse + u nll) + eps (dlse + (gamma_C sum|l| + u |sx|) / C + u |ls - sx / C|) + 3u |contrib|
+#   CE grad    p^ = expf(l - lse^): |dp| <= p (exp(dlse + u |l - lse|) - 1 + 2u);  g = w (p - y):  |dg| <= |w| (dp + u |p - y| + u) + 5u |g|
+U32 = 2.0 ** -24
+
+
+def _img_rows(x, P):
+    """[B, C, H, W] -> [B, nh*nw, C*P*P] patch rows (column order c, i, j), the adapters' out_proj layout."""
+    B, C, H, W = x.shape
+    return x.reshape(B, C, H // P, P, W // P, P).permute(0, 2, 4, 1, 3, 5).reshape(B, (H // P) * (W // P), C * P * P)
+
+
+def _rows_img(r, C, H, W, P):
+    B = r.shape[0]
+    return r.reshape(B, H // P, W // P, C, P, P).permute(0, 3, 1, 4, 2, 5).reshape(B, C, H, W)
+
+
+def _finish(s, bs, cnt, B, up):
+    """per-sample (sum, its bound), counts -> loss, its bound, nvalid, the fp64 weights up / (nvalid c_b)."""
+    valid = cnt > 0
+    nvalid = int(valid.sum())
+    q = torch.where(valid, s / cnt.clamp_min(1), torch.zeros_like(s))
+    dq = torch.where(valid, bs / cnt.clamp_min(1), torch.zeros_like(s))
+    loss = float(q.sum()) / nvalid if nvalid else 0.0
+    bl = (float(dq.sum()) + (gamma(B + 8) + 2 * U32) * float(q.abs().sum())) / nvalid if nvalid else 0.0
+    w = torch.where(valid, up / (max(nvalid, 1) * cnt.clamp_min(1)), torch.zeros_like(s))
+    return loss, bl, nvalid, w
+
+
+def pixel_loss_ref(kind: int, norm_pix: bool, pred, target, mask, P: int, up: float = 1.0):
+    """fp64 reference and bounds of mmae_masked_pixel_loss_* (kind 0 MSE, 1 L1) on pred / target [B, C, H, W] (any device), mask [B, nh*nw].
+    Returns a dict: mean / rstd [B, np] with bounds (norm_pix), sum [B] with bound, cnt [B] (exact), loss / nvalid, and the gradient
+    g [B, C, H, W] with bound bg; for L1 `amb` marks the elements whose sign the kernel may round either way."""
+    p, t = pred.double(), target.double()
+    B, C, H, W = t.shape
+    nval = C * P * P
+    m = mask.to(p.device).bool()
+    tr = _img_rows(t, P)
+    out = {}
+    if norm_pix:
+        mu = tr.mean(-1)
+        var = tr.var(-1)
+        rs = 1.0 / torch.sqrt(var + 1e-6)
+        e_mu = (gamma(nval) + U32) * tr.abs().mean(-1)
+        k = nval / (nval - 1)
+        dvar = (gamma(nval) + 4 * U32) * (var + k * e_mu ** 2) + k * e_mu ** 2 + U32 * 1e-6
+        r_rs = 0.51 * dvar / (var + 1e-6) + 3 * U32
+        out.update(mean=(mu, e_mu), rstd=(rs, r_rs * rs))
+        tn = (tr - mu[..., None]) * rs[..., None]
+        et = e_mu[..., None] * rs[..., None] * (1 + r_rs[..., None]) + (tr - mu[..., None]).abs() * rs[..., None] * (r_rs[..., None] + 2 * U32)
+        tn, et = _rows_img(tn, C, H, W, P), _rows_img(et, C, H, W, P)
+    else:
+        tn, et = t, torch.zeros_like(t)
+    d = p - tn
+    dd = et + U32 * (d.abs() + et)
+    if kind == 0:
+        e, de = d * d, 2 * d.abs() * dd + dd * dd + U32 * d * d
+    else:
+        e, de = d.abs(), dd
+    mi = m.reshape(B, H // P, W // P).repeat_interleave(P, 1).repeat_interleave(P, 2)[:, None].expand(B, C, H, W)
+    e, de = e * mi, de * mi
+    n = mi.flatten(1).sum(1).double()
+    s = e.flatten(1).sum(1) / C
+    bs = (de.flatten(1).sum(1) + (gamma(int(n.max()) + 16) + U32) * e.flatten(1).sum(1)) / C
+    cnt = m.sum(1).double() * P * P
+    loss, bl, nvalid, w = _finish(s, bs, cnt, B, up)
+    wc = (w / C)[:, None, None, None]
+    if kind == 0:
+        g = wc * 2 * d * mi
+        bg = (2 * wc.abs() * dd + 6 * U32 * g.abs()) * mi
+        amb = torch.zeros_like(mi)
+    else:
+        g = wc * torch.sign(d) * mi
+        bg = 6 * U32 * g.abs()
+        amb = mi & (d.abs() <= dd)
+    out.update(sum=(s, bs), cnt=cnt, loss=(loss, bl), nvalid=nvalid, g=g, bg=bg, amb=amb, w=wc * mi)
+    return out
+
+
+def ce_loss_ref(logits, target, mask, P: int, eps: float, up: float = 1.0, n_rescale=None):
+    """fp64 reference and bounds of mmae_masked_ce_* on logits [B, C, H, W], target [B, H, W] (outside [0, C): ignored, as
+    F.cross_entropy's ignore_index; the pixel still counts), mask [B, nh*nw].  Returns lse [B, H, W] with bound, sum [B] with bound,
+    cnt [B] (exact), loss / nvalid, the gradient g [B, C, H, W] with bound bg, and w (the weight per sample)."""
+    l = logits.double()
+    B, C, H, W = l.shape
+    tg = target.to(l.device)
+    ok = (tg >= 0) & (tg < C)
+    mi = mask.to(l.device).bool().reshape(B, H // P, W // P).repeat_interleave(P, 1).repeat_interleave(P, 2)
+    mx = l.amax(1)
+    rng = mx - l.amin(1)
+    lse = torch.logsumexp(l, 1)
+    if n_rescale is None:                             # image domain: a rescale needs a new running maximum -- at most the records of the row
+        cm = torch.cummax(l, 1).values
+        n_rescale = (l[:, 1:] > cm[:, :-1]).sum(1).double() + 1
+    r_s = gamma(C + 8) + 2 * U32 + 3 * U32 * n_rescale + 4 * U32 * rng
+    b_lse = 1.01 * r_s + 2 * U32 * (lse - mx).abs() + U32 * lse.abs()
+    lt = torch.gather(l, 1, torch.where(ok, tg, torch.zeros_like(tg))[:, None]).squeeze(1)
+    nll = lse - lt
+    mean_l = l.mean(1)
+    sm = lse - mean_l
+    contrib = (1 - eps) * nll + eps * sm
+    e_c = ((1 - eps) * (b_lse + U32 * nll.abs()) + eps * (b_lse + (gamma(C) * l.abs().sum(1) + U32 * l.sum(1).abs()) / C
+                                                        + U32 * sm.abs()) + 3 * U32 * contrib.abs())
+    use = mi & ok
+    contrib, e_c = contrib * use, e_c * use
+    n = mi.flatten(1).sum(1)
+    s = contrib.flatten(1).sum(1)
+    bs = e_c.flatten(1).sum(1) + (gamma(int(n.max()) + 16) + U32) * contrib.abs().flatten(1).sum(1)
+    cnt = mask.to(l.device).sum(1).double() * P * P
+    loss, bl, nvalid, w = _finish(s, bs, cnt, B, up)
+    pr = torch.exp(l - lse[:, None])
+    y = torch.zeros_like(l)
+    y.scatter_(1, torch.where(ok, tg, torch.zeros_like(tg))[:, None], 1.0)
+    y = (1 - eps) * y + eps / C
+    wc = w[:, None, None, None]
+    g = wc * (pr - y) * use[:, None]
+    dp = pr * (torch.expm1(b_lse[:, None] + U32 * (l - lse[:, None]).abs()) + 2 * U32)
+    bg = (wc.abs() * (dp + U32 * (pr - y).abs() + U32) + 5 * U32 * g.abs()) * use[:, None]
+    return dict(lse=(lse, b_lse), sum=(s, bs), cnt=cnt, loss=(loss, bl), nvalid=nvalid, g=g, bg=bg, w=w, mi=mi)

@@ -8,7 +8,8 @@ import math
 import pytest
 import torch
 
-from helpers import Guarded, assert_within, attention_bounds, gamma, poisoned, prod_bound, rel_err, ulp
+from helpers import (Guarded, assert_within, attention_bounds, ce_loss_ref, gamma, pixel_loss_ref, poisoned, prod_bound, rel_err,
+                     ulp)
 
 
 def _gemm():
@@ -136,3 +137,94 @@ def test_assert_within_reports_index_value_reference_and_bound():
     with pytest.raises(AssertionError, match=r'\(b=1, h=2, q=3, d=4\): value 0.5, reference 0.0, bound 1.000e-01'):
         assert_within(out, ref, 0.1, 'x', names=('b', 'h', 'q', 'd'))
     assert math.isfinite(float(prod_bound(torch.ones(1, 1), torch.ones(1, 1), 1).sum()))
+
+
+# ---- masked-loss references (pixel_loss_ref, ce_loss_ref) ----------------------------------------------------------------------
+def _pix_case(kind, norm_pix):
+    g = torch.Generator().manual_seed(3 + kind)
+    B, C, H, W, P = 4, 3, 64, 64, 8                 # 196 608 gradient elements
+    pred = torch.randn(B, C, H, W, generator=g)
+    target = torch.randn(B, C, H, W, generator=g)
+    target[:, :, :P, :P] = 0.1                       # a constant patch: var = 0
+    mask = (torch.rand(B, 64, generator=g) < 0.6).long()
+    mask[1] = 0
+    mask[0, 0] = 1
+    return pixel_loss_ref(kind, norm_pix, pred, target, mask, P, up=0.75), P
+
+
+def _ce_case(eps):
+    g = torch.Generator().manual_seed(5)
+    B, C, H, W, P = 2, 20, 32, 48, 4                 # 61 440 gradient elements
+    logits = torch.randn(B, C, H, W, generator=g) * 3
+    target = torch.randint(0, C, (B, H, W), generator=g)
+    target[:, ::5, ::3] = 255                        # ignored
+    mask = (torch.rand(B, (H // P) * (W // P), generator=g) < 0.6).long()
+    return ce_loss_ref(logits, target, mask, P, eps, up=1.25), P
+
+
+@pytest.mark.parametrize('kind,norm_pix', [(0, False), (0, True), (1, False), (1, True)])
+def test_pixel_loss_bounds_pass_the_rounded_exact_result(kind, norm_pix):
+    ref, _ = _pix_case(kind, norm_pix)
+    for dt in (torch.float32, torch.bfloat16):
+        out = ref['g'].to(dt).double()
+        extra = ulp(dt, ref['g'].abs() + ref['bg']) / 2 if dt != torch.float32 else 0
+        assert_within(out, ref['g'], ref['bg'] + extra + (ref['g'].abs() * 2.0 ** -24 if dt == torch.float32 else 0), f'gradient as {dt}')
+    assert_within(ref['sum'][0].float(), ref['sum'][0], ref['sum'][1], 'per-sample sum as f32')
+    if norm_pix:
+        for k in ('mean', 'rstd'):
+            assert_within(ref[k][0].float(), ref[k][0], ref[k][1], f'{k} as f32')
+
+
+def test_ce_bounds_pass_the_rounded_exact_result():
+    for eps in (0.0, 0.1, 1.0):
+        ref, _ = _ce_case(eps)
+        assert_within(ref['g'].float(), ref['g'], ref['bg'], f'eps {eps} d_logits as f32')
+        assert_within(ref['lse'][0].float(), ref['lse'][0], ref['lse'][1], f'eps {eps} lse as f32')
+        assert_within(ref['sum'][0].float(), ref['sum'][0], ref['sum'][1], f'eps {eps} per-sample sum as f32')
+
+
+def _corrupt(x, how, P):
+    x = x.clone()
+    if how == 'element':
+        i = int(torch.nonzero(x.reshape(-1))[len(torch.nonzero(x.reshape(-1))) // 2])
+        x.view(-1)[i] *= 1 + 2e-3
+    elif how == 'patch':                              # one patch of one sample, every channel: a weight off by 5e-5
+        b = int(torch.nonzero(x.flatten(1).abs().sum(1))[0])
+        nz = torch.nonzero(x[b, 0])[-1]
+        y0, x0 = int(nz[0]) // P * P, int(nz[1]) // P * P
+        x[b, :, y0:y0 + P, x0:x0 + P] *= 1 + 5e-5
+    else:                                             # the tail: last 8 non-zero elements off by 3e-4
+        idx = torch.nonzero(x.reshape(-1)).reshape(-1)[-8:]
+        x.view(-1)[idx] *= 1 + 3e-4
+    return x
+
+
+@pytest.mark.parametrize('how', ['element', 'patch', 'tail'])
+def test_masked_loss_gradient_corruptions_are_flagged_though_rel_l2_passes(how):
+    ref, P = _pix_case(0, True)
+    bad = _corrupt(ref['g'], how, P).float()
+    assert rel_err(bad, ref['g']) < 1e-5               # test_masked_pixel_losses' tolerance on the gradient
+    with pytest.raises(AssertionError, match='outside the bound'):
+        assert_within(bad, ref['g'], ref['bg'] + ref['g'].abs() * 2.0 ** -24, f'MSE norm_pix gradient, {how} corrupted')
+    cref, P = _ce_case(0.1)
+    bad = _corrupt(cref['g'], how, P).float()
+    assert rel_err(bad, cref['g']) < 4e-3              # test_masked_cross_entropy_label_smoothing's tolerance
+    with pytest.raises(AssertionError, match='outside the bound'):
+        assert_within(bad, cref['g'], cref['bg'], f'CE gradient, {how} corrupted')
+
+
+def test_ce_lse_of_one_pixel_off_and_an_ignored_target_read_are_flagged():
+    ref, P = _ce_case(0.1)
+    lse = ref['lse'][0].float().clone()
+    lse[1, 7, 9] += 1e-4
+    assert rel_err(lse, ref['lse'][0]) < 1e-5
+    with pytest.raises(AssertionError, match='outside the bound'):
+        assert_within(lse, ref['lse'][0], ref['lse'][1], 'lse')
+    # a kernel that read the logits at an ignored pixel's clamped target (class 0) instead of skipping it
+    g = ref['g'].clone()
+    y, x = (int(v) for v in torch.nonzero(ref['mi'][0, ::5, ::3])[0])
+    y, x = 5 * y, 3 * x                               # an ignored pixel (target[:, ::5, ::3] = 255) inside a masked patch
+    assert bool((g[0, :, y, x] == 0).all())
+    g[0, 0, y, x] -= ref['w'][0] * 0.9
+    with pytest.raises(AssertionError, match='outside the bound'):
+        assert_within(g.float(), ref['g'], ref['bg'], 'CE gradient at an ignored pixel')
