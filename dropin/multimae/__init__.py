@@ -6,6 +6,11 @@
     from multimae.input_adapters import PatchedInputAdapter, SemSegInputAdapter
     from multimae.output_adapters import SpatialOutputAdapter
 
+and the semantic-segmentation fine-tuning script's import lines (run_finetuning_semseg.py:36-39):
+
+    from multimae.output_adapters import (ConvNeXtAdapter, DPTOutputAdapter,
+                                          SegmenterMaskTransformerAdapter)   # DPT / Segmenter: names only, constructing one raises
+
 (reference import surface: run_pretraining_multimae.py:36-40, multimae/__init__.py)."""
 import os
 import sys

@@ -920,6 +920,38 @@ int64_t mmae_x3_tmp_bytes(int64_t rows, int cols);
 int mmae_probe_tr16(const uint16_t* lds_image_1024, const uint32_t* lane_byte_addr_64, uint16_t* out_64x4,
                     void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * ConvNeXt semantic-segmentation head (ConvNeXtAdapter, output_adapters.py:481-573; ConvNeXtBlock, output_adapter_utils.py:19-57),
+ * csrc/convnext.hip.  The feature map is f32 channels-last [B][h][w][C] (h = NH s, w = NW s, s^2 = preds_per_patch): LayerNorm and
+ * the 1 x 1 convolutions are mmae_layernorm_* and mmae_gemm on its pixel rows; what is not a row op is here.  No float atomics.
+ *   rows_gather:   adapt_tokens + torch.cat (output_adapters.py:542-550) for one main task: out[b N + n][col_off + d] =
+ *                  enc[b][start + n][d] (enc f32 [B][n_tok][D]; out f32 / bf16, row stride ld_out).
+ *   rows_scatter:  its backward: d_enc[b][start + n][d] = src[b N + n][col_off + d]; other rows untouched (the caller zeroes them).
+ *   shuffle_fwd:   the two rearranges of output_adapters.py:558-563: map[b][nh s + ph][nw s + pw][c] = proj[b][nh NW + nw][(ph s + pw) C + c];
+ *   shuffle_bwd:   the inverse copy d_map -> d_proj.  Both bit-exact.
+ *   dwconv7_fwd:   ConvNeXtBlock.dwconv (output_adapter_utils.py:37,46): y = depthwise 7 x 7 conv of x (padding 3) + bias, w7 = the
+ *                  (C, 1, 7, 7) weight.  Any h, w, C >= 1.
+ *   dwconv7_dgrad: dx_out = dx_in + dwconv^T(dy) -- the block's residual gradient (output_adapter_utils.py:56) in the same pass; dx_in may be NULL.
+ *   dwconv7_wgrad: part[nblk][C * 49] (nblk = mmae_dwconv7_wgrad_nblk) of per-workgroup sums of dy . x_shifted in w7's layout; sum the rows
+ *                  with mmae_colsum_partials.  The bias gradient is the colsum segment of mmae_layernorm_bwd's partials.
+ *   resize_fwd:    F.interpolate(size=(H, W), mode) of output_adapters.py:568, mode 0 = bilinear, 1 = nearest, align_corners = False,
+ *                  scale = in / out (PyTorch's index and border-clamp formulas): x f32 [B][h][w][K] (row stride ldx) -> out f32 [B][K][H][W].
+ *   resize_bwd:    its backward as a gather, each low-resolution element summing its output window in a fixed order: g [B][K][H][W] ->
+ *                  dx f32 [B][h][w][ldx], columns K .. ldx - 1 written as zeros (padding of the next GEMM operand).
+ * ------------------------------------------------------------------------- */
+int mmae_convnext_rows_gather(const float* enc, void* out, int out_dtype, int B, int n_tok, int D, int start, int N, int64_t ld_out, int col_off,
+                              void* stream);
+int mmae_convnext_rows_scatter(const void* src, int src_dtype, float* d_enc, int B, int n_tok, int D, int start, int N, int64_t ld_src, int col_off,
+                               void* stream);
+int mmae_convnext_shuffle_fwd(const float* proj, float* map, int B, int NH, int NW, int s, int C, void* stream);
+int mmae_convnext_shuffle_bwd(const float* d_map, float* d_proj, int B, int NH, int NW, int s, int C, void* stream);
+int mmae_dwconv7_fwd(const float* x, const float* w7, const float* bias, float* y, int B, int h, int w, int C, void* stream);
+int mmae_dwconv7_dgrad(const float* dy, const float* w7, const float* dx_in, float* dx_out, int B, int h, int w, int C, void* stream);
+int mmae_dwconv7_wgrad_nblk(int B, int h, int w);
+int mmae_dwconv7_wgrad(const float* x, const float* dy, float* part, int B, int h, int w, int C, void* stream);
+int mmae_resize_fwd(const float* x, int64_t ldx, float* out, int B, int h, int w, int K, int H, int W, int mode, void* stream);
+int mmae_resize_bwd(const float* g, float* dx, int64_t ldx, int B, int h, int w, int K, int H, int W, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1218,3 +1218,101 @@ class MaskedCEPatFn(torch.autograd.Function):
                                                      ops._stream()), 'masked_ce_pat_bwd')
         h.d_pat = d_pat if h.d_pat is None else h.d_pat.add_(d_pat)
         return up.new_empty(1), None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------
+# ConvNeXt semantic-segmentation head (ConvNeXtAdapter, output_adapters.py:481-573)
+# ------------------------------------------------------------------------------------------
+CONVNEXT_BLOCK_PARAMS = ('dwconv.weight', 'dwconv.bias', 'norm.weight', 'norm.bias', 'pwconv1.weight', 'pwconv1.bias', 'pwconv2.weight',
+                         'pwconv2.bias')
+
+
+class ConvNeXtHeadFn(torch.autograd.Function):
+    """The whole head as ONE autograd node: token rows -> proj_dec -> pixel shuffle -> depth x ConvNeXtBlock -> final_layer ->
+    F.interpolate.  The map is f32 channels-last [B h w, C]; LayerNorm and the 1 x 1 convolutions run on its pixel rows
+    (mmae_layernorm_*, mmae_gemm with the bias + GELU' pair and the bias + residual epilogues), the depthwise 7 x 7 convolutions,
+    the shuffle and the resize on csrc/convnext.hip.  params: CONVNEXT_BLOCK_PARAMS per block, then final_layer.{weight, bias},
+    proj_dec.{weight, bias}."""
+
+    @staticmethod
+    def forward(ctx, cfg: _Cfg, enc: Tensor, *params: Tensor):
+        ops._require_gpu(enc, 'ConvNeXt head input')
+        act, wc = cfg.act, cfg.wc
+        B, n_tok, D = enc.shape
+        N, NH, NW, s, C, K, H, W, depth = cfg.N, cfg.NH, cfg.NW, cfg.s, cfg.C, cfg.K, cfg.H, cfg.W, cfg.depth
+        h, w, R, TD = NH * s, NW * s, B * NH * s * NW * s, len(cfg.starts) * D
+        f32 = torch.float32
+        enc = enc.detach().contiguous().float()
+        fw, fb, pw, pb = params[8 * depth:8 * depth + 4]
+        x_tok = _new((B * N, TD), enc, act)
+        for t, st in enumerate(cfg.starts):                       # adapt_tokens + torch.cat (:542-550)
+            ops.convnext_rows_gather(enc, x_tok, st, N, t * D)
+        proj = ops.linear_fwd(x_tok, wc(pw), pb.detach(), _new((B * N, s * s * C), enc, f32))          # proj_dec (:556)
+        x = ops.convnext_shuffle(proj, _new((R, C), enc, f32), B, NH, NW, s, C)                     # rearranges (:557-563)
+        del proj
+        saved = []
+        for i in range(depth):                                    # ConvNeXtBlock.forward (output_adapter_utils.py:44-57)
+            dww, dwb, gam, bet, w1, b1, w2, b2 = params[8 * i:8 * i + 8]
+            t = ops.dwconv7_fwd(x, dww.detach(), dwb.detach(), torch.empty_like(x), B, h, w, C)
+            n, mean, rstd = ops.layernorm_fwd(t, gam.detach(), bet.detach(), cfg.eps, act)
+            gp = _new((R, 4 * C), enc, act)                       # GELU'(pre-activation) for the backward epilogue
+            h1 = ops.linear_fwd(n, wc(w1), b1.detach(), _new((R, 4 * C), enc, act), aux=gp, epi=ops.EPI_GELU_G)
+            y = ops.linear_fwd(h1, wc(w2), b2.detach(), _new((R, C), enc, f32), resid=x)
+            saved.append((x, t, mean, rstd, n, h1, gp))
+            x = y
+        Kp = ops.round_up(K, 8)                                   # a GEMM operand's row stride: the logits gradient is one
+        xa = ops.cast(x, act)
+        logits = _new((R, Kp), enc, f32)
+        ops.gemm(xa, wc(fw).view(K, C), logits, R, K, C, lda=C, ldb=C, ldc=Kp, bias=fb.detach())   # final_layer (:566)
+        out = ops.resize_fwd(logits, Kp, _new((B, K, H, W), enc, f32), B, h, w, K, H, W, cfg.mode)  # F.interpolate (:568)
+        ctx.cfg, ctx.params, ctx.saved, ctx.rest = cfg, params, saved, (x_tok, xa, n_tok, D, Kp)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        cfg, params = ctx.cfg, ctx.params
+        x_tok, xa, n_tok, D, Kp = ctx.rest
+        act, wc = cfg.act, cfg.wc
+        N, NH, NW, s, C, K, H, W, depth = cfg.N, cfg.NH, cfg.NW, cfg.s, cfg.C, cfg.K, cfg.H, cfg.W, cfg.depth
+        h, w = NH * s, NW * s
+        B = d_out.shape[0]
+        R = B * h * w
+        f32 = torch.float32
+        sink = GradSink(engine.direct_grads())
+        grads: List[Optional[Tensor]] = [None] * len(params)
+        fw, fb, pw, pb = params[8 * depth:8 * depth + 4]
+        g = d_out.contiguous().float()
+        d_log = ops.resize_bwd(g, _new((R, Kp), g, f32), Kp, B, h, w, K, H, W, cfg.mode)
+        d_log = ops.cast(d_log, act)[:, :K]                       # row stride Kp, zero columns K .. Kp - 1
+        dx = ops.linear_dx(d_log, wc(fw).view(K, C), _new((R, C), g, f32))
+        grads[8 * depth], grads[8 * depth + 1] = sink.linear(fw, fb, d_log, xa)
+        for i in reversed(range(depth)):
+            x_in, t, mean, rstd, n, h1, gp = ctx.saved[i]
+            dww, dwb, gam, bet, w1, b1, w2, b2 = params[8 * i:8 * i + 8]
+            dy = dx                                               # gradient of the block output = of its residual input
+            dy_a = ops.cast(dy, act)
+            d_pre = ops.linear_dx(dy_a, wc(w2), _new((R, 4 * C), g, act), aux=gp, epi=ops.EPI_MUL)
+            d_n = ops.linear_dx(d_pre, wc(w1), _new((R, C), g, f32))
+            grads[8 * i + 6], grads[8 * i + 7] = sink.linear(w2, b2, dy_a, h1)
+            grads[8 * i + 4], grads[8 * i + 5] = sink.linear(w1, b1, d_pre, n)
+            del d_pre, h1, gp
+            dt, _, part = ops.layernorm_bwd_part(d_n, t, gam.detach(), mean, rstd, None, None)
+            del d_n
+            # [dgamma | dbeta | colsum(dt)]: the last segment is dwconv's bias gradient
+            grads[8 * i + 2], grads[8 * i + 3], grads[8 * i + 1] = sink.colsums(part, C, [gam, bet, dwb])
+            if dww.requires_grad:
+                gdw = ops.reduce_partials(ops.dwconv7_wgrad(x_in, dt, B, h, w, C), _new((C * 49,), g, f32), False)
+                grads[8 * i] = sink.vec(dww, gdw)
+            dx = ops.dwconv7_dgrad(dt, dww.detach(), dy, torch.empty_like(dy), B, h, w, C)
+            ctx.saved[i] = None
+        d_proj = ops.convnext_shuffle(dx, _new((B * N, s * s * C), g, f32), B, NH, NW, s, C, inverse=True)
+        dp_a = ops.cast(d_proj, act)
+        d_enc = None
+        if ctx.needs_input_grad[1]:
+            d_tok = ops.linear_dx(dp_a, wc(pw), _new((B * N, x_tok.shape[1]), g, f32))
+            d_enc = torch.zeros((B, n_tok, D), device=g.device, dtype=f32)         # rows of other tasks and global tokens: 0
+            for t_, st in enumerate(cfg.starts):
+                ops.convnext_rows_scatter(d_tok, d_enc, st, N, t_ * D)
+        grads[8 * depth + 2], grads[8 * depth + 3] = sink.linear(pw, pb, dp_a, x_tok)
+        ctx.saved = ctx.params = ctx.rest = None
+        return (None, d_enc, *grads)

@@ -1463,3 +1463,60 @@ def opt_step_groups(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, i
         host = (ctypes.c_float * len(hyper))(*hyper)       # copied into the launch's arguments during the call
         d.hyper = ctypes.addressof(host)
     check(_lib.load().mmae_opt_step_groups(ctypes.byref(d), _stream()), 'opt_step_groups')
+
+
+# ------------------------------------------------------------------ ConvNeXt head (csrc/convnext.hip) --
+def convnext_rows_gather(enc: Tensor, out: Tensor, start: int, N: int, col_off: int) -> None:
+    """out[b N + n][col_off + d] = enc[b][start + n][d]; enc f32 [B, n_tok, D] contiguous, out f32 / bf16 2-D."""
+    B, n_tok, D = enc.shape
+    check(_lib.load().mmae_convnext_rows_gather(enc.data_ptr(), out.data_ptr(), dcode(out.dtype), B, n_tok, D, start, N, out.stride(0),
+                                                col_off, _stream()), 'convnext_rows_gather')
+
+
+def convnext_rows_scatter(src: Tensor, d_enc: Tensor, start: int, N: int, col_off: int) -> None:
+    """d_enc[b][start + n][d] = src[b N + n][col_off + d] (the rows of other tasks are left as they are)."""
+    B, n_tok, D = d_enc.shape
+    check(_lib.load().mmae_convnext_rows_scatter(src.data_ptr(), dcode(src.dtype), d_enc.data_ptr(), B, n_tok, D, start, N, src.stride(0),
+                                                 col_off, _stream()), 'convnext_rows_scatter')
+
+
+def convnext_shuffle(src: Tensor, dst: Tensor, B: int, NH: int, NW: int, s: int, C: int, inverse: bool = False) -> Tensor:
+    """proj [B, NH NW, s s C] -> map [B, NH s, NW s, C] (inverse: the way back); f32, contiguous."""
+    lib = _lib.load()
+    fn = lib.mmae_convnext_shuffle_bwd if inverse else lib.mmae_convnext_shuffle_fwd
+    check(fn(src.data_ptr(), dst.data_ptr(), B, NH, NW, s, C, _stream()), 'convnext_shuffle')
+    return dst
+
+
+def dwconv7_fwd(x: Tensor, w7: Tensor, bias: Optional[Tensor], out: Tensor, B: int, h: int, w: int, C: int) -> Tensor:
+    check(_lib.load().mmae_dwconv7_fwd(x.data_ptr(), w7.data_ptr(), _p(bias), out.data_ptr(), B, h, w, C, _stream()), 'dwconv7_fwd')
+    return out
+
+
+def dwconv7_dgrad(dy: Tensor, w7: Tensor, dx_in: Optional[Tensor], out: Tensor, B: int, h: int, w: int, C: int) -> Tensor:
+    check(_lib.load().mmae_dwconv7_dgrad(dy.data_ptr(), w7.data_ptr(), _p(dx_in), out.data_ptr(), B, h, w, C, _stream()), 'dwconv7_dgrad')
+    return out
+
+
+def dwconv7_wgrad(x: Tensor, dy: Tensor, B: int, h: int, w: int, C: int) -> Tensor:
+    """the UNREDUCED weight-gradient partials f32 [nblk, C * 49] (reduce with colsum / reduce_partials)"""
+    lib = _lib.load()
+    nblk = max(1, int(lib.mmae_dwconv7_wgrad_nblk(B, h, w)))
+    part = torch.empty((nblk, C * 49), device=x.device, dtype=torch.float32)
+    check(lib.mmae_dwconv7_wgrad(x.data_ptr(), dy.data_ptr(), part.data_ptr(), B, h, w, C, _stream()), 'dwconv7_wgrad')
+    return part
+
+
+RESIZE_MODES = {'bilinear': 0, 'nearest': 1}
+
+
+def resize_fwd(x: Tensor, ldx: int, out: Tensor, B: int, h: int, w: int, K: int, H: int, W: int, mode: str) -> Tensor:
+    """F.interpolate(size=(H, W), mode, align_corners=False): x f32 [B, h, w, ldx] (first K columns) -> out f32 [B, K, H, W]"""
+    check(_lib.load().mmae_resize_fwd(x.data_ptr(), ldx, out.data_ptr(), B, h, w, K, H, W, RESIZE_MODES[mode], _stream()), 'resize_fwd')
+    return out
+
+
+def resize_bwd(g: Tensor, dx: Tensor, ldx: int, B: int, h: int, w: int, K: int, H: int, W: int, mode: str) -> Tensor:
+    """its backward: g f32 [B, K, H, W] -> dx f32 [B, h, w, ldx] (columns K .. ldx - 1 zeroed)"""
+    check(_lib.load().mmae_resize_bwd(g.data_ptr(), dx.data_ptr(), ldx, B, h, w, K, H, W, RESIZE_MODES[mode], _stream()), 'resize_bwd')
+    return dx

@@ -9,20 +9,22 @@ backward are fixed HIP kernel sequences; the (B, N_total, D) mask-token tensor o
 reference is never materialised.
 
 LinearOutputAdapter (output_adapters.py:285-356, the classification head of the MultiViT fine-tuning forward,
-SURVEY.md section 8f row 4) is built on the same kernels.  The dense-prediction fine-tuning heads (Segmenter / ConvNeXt /
-DPT adapters) are out of scope for the pre-training hot path.
+SURVEY.md section 8f row 4) is built on the same kernels.  ConvNeXtAdapter (output_adapters.py:481-573, the default head of
+run_finetuning_semseg.py) is one autograd node (functions.ConvNeXtHeadFn) on the row kernels, the GEMMs and csrc/convnext.hip.
+The other dense-prediction heads (DPTOutputAdapter, SegmenterMaskTransformerAdapter) are not built: their names exist so that
+the semseg script's import line works, and constructing one raises NotImplementedError.
 """
 from __future__ import annotations
 
 from functools import partial
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, Iterable, Optional, Tuple, Union
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import engine
-from .functions import SpatialAdapterFn, TokenMeanFn
+from .functions import ConvNeXtHeadFn, SpatialAdapterFn, TokenMeanFn
 from .multimae_utils import (Block, CrossAttention, LayerNorm, Linear, Mlp, _as_hip_norm, _cfg, bias_or_zero, block_params,
                              build_2d_sincos_posemb, pair, trunc_normal_)
 
@@ -242,3 +244,107 @@ class LinearOutputAdapter(nn.Module):
         else:
             x = encoder_tokens[:, -1]                       # the global token is appended last (multimae.py:344-347)
         return self.head(self.norm(x))
+
+
+class ConvNeXtBlock(nn.Module):
+    """Parameter container of the reference's ConvNeXtBlock(dim) (output_adapter_utils.py:19-57) as ConvNeXtAdapter builds it: no layer
+    scale, no drop path.  Same modules in the same order, so construction draws the same random numbers.  The computation is
+    ConvNeXtHeadFn's (the head runs as one node)."""
+
+    def __init__(self, dim: int):
+        super().__init__()
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
+        self.norm = LayerNorm(dim, eps=1e-6)
+        self.pwconv1 = Linear(dim, 4 * dim)
+        self.pwconv2 = Linear(4 * dim, dim)
+
+
+class ConvNeXtAdapter(nn.Module):
+    """ConvNeXt semantic-segmentation head (output_adapters.py:481-573): the main tasks' token rows concatenated along features,
+    proj_dec, a pixel shuffle into a map of C = embed_dim / preds_per_patch channels at sqrt(preds_per_patch) times the token grid,
+    `depth` ConvNeXt blocks, a 1 x 1 final_layer and F.interpolate to the image size.  Same constructor, parameter names,
+    registration order and seeded initialisation as the reference (proj_dec registered last, in init())."""
+
+    def __init__(self, num_classes, embed_dim: int = 6144, preds_per_patch: int = 16, main_tasks: Iterable[str] = ('rgb',),
+                 patch_size: int = 16, depth: int = 4, interpolate_mode: str = 'bilinear', **kwargs):
+        super().__init__()
+        s = int(round(preds_per_patch ** 0.5))
+        if preds_per_patch < 1 or s * s != preds_per_patch:
+            raise ValueError(f'ConvNeXtAdapter: preds_per_patch = {preds_per_patch} is not a perfect square')
+        if embed_dim % preds_per_patch != 0:
+            raise ValueError(f'ConvNeXtAdapter: embed_dim = {embed_dim} is not a multiple of preds_per_patch = {preds_per_patch}')
+        if interpolate_mode not in ('bilinear', 'nearest'):
+            raise NotImplementedError(f'ConvNeXtAdapter: interpolate_mode {interpolate_mode!r} is not built (bilinear, nearest)')
+        self.main_tasks = main_tasks
+        self.patch_size = patch_size
+        self.embed_dim = embed_dim
+        self.preds_per_patch = preds_per_patch
+        self.class_dim = embed_dim // preds_per_patch
+        self.num_classes = num_classes
+        self.interpolate_mode = interpolate_mode
+        self.blocks = nn.Sequential(*[ConvNeXtBlock(dim=self.class_dim) for _ in range(depth)])
+        self.final_layer = nn.Conv2d(self.class_dim, self.num_classes, 1)
+        self.apply(self._init_weights)
+
+    def init(self, dim_tokens_enc: int = 768):
+        self.in_channels = dim_tokens_enc * len(self.main_tasks)
+        self.proj_dec = Linear(self.in_channels, self.embed_dim)
+        self._init_weights(self.proj_dec)
+
+    def _init_weights(self, m):
+        if isinstance(m, nn.Linear):
+            trunc_normal_(m.weight, std=.02)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+        elif isinstance(m, nn.LayerNorm):
+            nn.init.constant_(m.bias, 0)
+            nn.init.constant_(m.weight, 1.0)
+
+    def _params(self):
+        ps = []
+        for b in self.blocks:
+            ps += [b.dwconv.weight, b.dwconv.bias, b.norm.weight, b.norm.bias, b.pwconv1.weight, b.pwconv1.bias, b.pwconv2.weight,
+                   b.pwconv2.bias]
+        return ps + [self.final_layer.weight, self.final_layer.bias, self.proj_dec.weight, self.proj_dec.bias]
+
+    def forward(self, encoder_tokens: torch.Tensor, input_info: Dict):
+        """(B, N_total, D) encoder tokens -> f32 (B, num_classes, H, W) logits (output_adapters.py:552-570)."""
+        H, W = input_info['image_size']
+        NH, NW = H // self.patch_size, W // self.patch_size
+        starts, counts = [], []
+        for task in self.main_tasks:
+            info = input_info['tasks'][task]
+            starts.append(int(info['start_idx']))
+            counts.append(int(info['end_idx']) - int(info['start_idx']))
+        if len(set(counts)) != 1 or counts[0] != NH * NW:
+            raise ValueError(f'ConvNeXtAdapter: the main tasks {tuple(self.main_tasks)} have {counts} tokens; each needs the '
+                             f'{NH} x {NW} grid of the {H} x {W} image')
+        D = encoder_tokens.shape[-1]
+        if D * len(starts) != self.in_channels:
+            raise ValueError(f'ConvNeXtAdapter: encoder width {D} x {len(starts)} tasks != proj_dec input {self.in_channels}')
+        C = self.class_dim
+        cfg = _cfg(self, starts=starts, N=NH * NW, NH=NH, NW=NW, s=int(round(self.preds_per_patch ** 0.5)), C=C, K=self.num_classes,
+                   H=H, W=W, depth=len(self.blocks), mode=self.interpolate_mode, eps=1e-6)
+        if C % 4 or C > 1024:
+            raise ValueError(f'ConvNeXtAdapter: the LayerNorm kernel needs embed_dim / preds_per_patch ({C}) to be a multiple of 4 '
+                             'in [4, 1024]')
+        if cfg.act != torch.float32 and (C % 8 or self.in_channels % 8):
+            raise ValueError(f'ConvNeXtAdapter: the bf16 GEMMs need embed_dim / preds_per_patch ({C}) and the concatenated token width '
+                             f'({self.in_channels}) to be multiples of 8; use engine.set_precision("fp32") for this geometry')
+        return ConvNeXtHeadFn.apply(cfg, encoder_tokens, *self._params())
+
+
+class DPTOutputAdapter(nn.Module):
+    """Name only (output_adapters.py:576-...): the DPT head is not built in this engine."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError('DPTOutputAdapter (the DPT semantic-segmentation head) is not built in multimae_amd; '
+                                  'use ConvNeXtAdapter (--output_adapter convnext)')
+
+
+class SegmenterMaskTransformerAdapter(nn.Module):
+    """Name only (output_adapters.py:359-478): the Segmenter mask-transformer head is not built in this engine."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError('SegmenterMaskTransformerAdapter (the Segmenter semantic-segmentation head) is not built in '
+                                  'multimae_amd; use ConvNeXtAdapter (--output_adapter convnext)')
