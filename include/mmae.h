@@ -49,7 +49,9 @@ extern "C" {
                           counted optimiser step (mmae_opt_step's non-finite test), as under fp16 autocast.  GRADIENT tensors are stored multiplied
                           by S = 2^(4 - floor(log2 m)), m = the device scalar `dy_amax` the loss backward wrote (an upper bound of
                           |dL/dprediction|): the largest element sits in [16, 32), 11 bits of head-room above and 2^-18..2^-28 of it
-                          below; the f32 sinks (weight / bias / LayerNorm / token gradients, d_enc) multiply by 1/S.  Accepted by:
+                          below; the f32 sinks (weight / bias / LayerNorm / token gradients, d_enc) multiply by 1/S.  The formula is
+                          applied for 2^-119 <= m < 2^127 (S and 1/S then stay normal powers of two with room to spare); for any other
+                          m -- zero, a subnormal, below 2^-119, 2^127 and above, inf, NaN -- and without the scalar, S = 1.  Accepted by:
                           mmae_gemm (ab/c/aux dtype, ping-pong kernels with a compiled epilogue flavour only), mmae_gemm_dw_group,
                           mmae_layernorm_*, mmae_colsum*, mmae_cast_f32_to_f16 / _f16_to_f32, mmae_attn_*_f16, mmae_masked_ce_pat_bwd (the
                           one loss whose gradient is bounded before it is written; any other gradient enters through the scaled cast),
@@ -575,7 +577,7 @@ int mmae_cast_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
  * way (an f32 loss gradient entering the fp16-storage domain), fp16 -> f32 by 1/S. */
 int mmae_cast_f32_to_f16(const float* src, void* dst, int64_t n, const float* scale_amax, void* stream);
 int mmae_cast_f16_to_f32(const void* src, float* dst, int64_t n, const float* scale_amax, void* stream);
-/* dst[c][r] = src[r][c], src f32 [rows][cols]; dst act dtype [cols][rows] */
+/* dst[c][r] = src[r][c], src f32 [rows][cols]; dst [cols][rows], dst_dtype MMAE_F32 or MMAE_BF16 (any other code is refused) */
 int mmae_transpose_cast(const float* src, void* dst, int dst_dtype, int rows, int cols, void* stream);
 /* mean pooling over tokens, LinearOutputAdapter.forward (output_adapters.py:346-347):  y[b][:] = mean_n x[b][n][:]
  * (x f32 [B][N][D], y f32 [B][D]) and its backward dx[b][n][:] = dy[b][:] / N. */
@@ -782,7 +784,10 @@ int mmae_masked_ce_pat_bwd(const float* pat, const int64_t* target, const int64_
  * utils/optim_factory.py:138-174 (decoupled weight decay on every tensor).
  *   mmae_sumsq: out[0] (+)= sum x^2   (ws: f32 scratch >= 1024 elements)
  *   mmae_adamw: p,g,m,v f32 [n]; grad_scale multiplies g first (clipping);
- *               optional act-dtype shadow of the updated parameters.
+ *               optional shadow of the updated parameters: shadow_dtype MMAE_F32 (16-byte aligned) or MMAE_BF16 (8-byte
+ *               aligned, round to nearest even) -- the two flavours the kernels have; any other code (MMAE_F16 included) or a
+ *               misaligned shadow is refused with MMAE_EINVAL before anything is launched or written.  The same rule holds for
+ *               mmae_adamw_dev, mmae_opt_step and mmae_opt_step_groups.
  *               If skip_flag (device int32) is non-null and *skip_flag != 0 the step
  *               is a no-op (non-finite / skip_grad handling without a host sync).
  * ------------------------------------------------------------------------- */
@@ -819,7 +824,7 @@ int mmae_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, cons
  * ------------------------------------------------------------------------- */
 typedef struct mmae_opt_desc {
     float* p; const float* g; float* m; float* v; int64_t n;
-    void* shadow; int32_t shadow_dtype;          /* optional act-dtype copy of the updated parameters */
+    void* shadow; int32_t shadow_dtype;          /* optional copy of the updated parameters: MMAE_F32 / MMAE_BF16 only (mmae_adamw) */
     float lr, weight_decay, beta1, beta2, eps;
     const float* lrwd_dev;
     float clip_grad, skip_grad, grad_prescale;

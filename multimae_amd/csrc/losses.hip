@@ -671,6 +671,14 @@ int launch_adamw_groups(const mmae_opt_groups_desc* d, const HY& hy, hipStream_t
     return mmae_check_launch("adamw_groups");
 }
 
+// The shadow has a kernel flavour for f32 and for bf16 only, and the vector path stores it four elements at a time (st4): any
+// other dtype code used to take the f32 kernel and write 4-byte values into whatever buffer it was given.
+inline bool shadow_ok(const void* shadow, int dtype) {
+    if (!shadow) return true;
+    return (dtype == MMAE_F32 && (uintptr_t)shadow % 16 == 0) || (dtype == MMAE_BF16 && (uintptr_t)shadow % 8 == 0);
+}
+#define MMAE_SHADOW_MSG ": shadow must be MMAE_F32 (16-byte aligned) or MMAE_BF16 (8-byte aligned)"
+
 }  // namespace
 
 extern "C" {
@@ -824,6 +832,7 @@ int mmae_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr
                void* stream) {
     MMAE_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adamw: bad argument");
     MMAE_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "adamw: unaligned");
+    MMAE_REQUIRE(shadow_ok(shadow, shadow_dtype), "adamw" MMAE_SHADOW_MSG);
     const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
     const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     long long nb = cdiv64(n, 1024);
@@ -840,6 +849,7 @@ int mmae_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, cons
                    const float* grad_scale_dev, const int32_t* skip_flag, void* shadow, int shadow_dtype, void* stream) {
     MMAE_REQUIRE(p && g && m && v && n > 0 && hyper_dev, "adamw_dev: bad argument");
     MMAE_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0), "adamw_dev: unaligned");
+    MMAE_REQUIRE(shadow_ok(shadow, shadow_dtype), "adamw_dev" MMAE_SHADOW_MSG);
     long long nb = cdiv64(n, 1024);
     if (nb > 8192) nb = 8192;
     hipStream_t st = (hipStream_t)stream;
@@ -853,6 +863,8 @@ int mmae_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, cons
 int mmae_opt_step(const mmae_opt_desc* d, void* stream) {
     MMAE_REQUIRE(d && d->p && d->g && d->m && d->v && d->n > 0 && d->state && d->istate && d->ws, "opt_step: bad argument");
     MMAE_REQUIRE(d->grad_prescale > 0.f, "opt_step: grad_prescale must be positive (1 for a single process)");
+    MMAE_REQUIRE(((uintptr_t)d->p % 16 == 0) && ((uintptr_t)d->g % 16 == 0) && ((uintptr_t)d->m % 16 == 0) && ((uintptr_t)d->v % 16 == 0), "opt_step: unaligned");
+    MMAE_REQUIRE(shadow_ok(d->shadow, d->shadow_dtype), "opt_step" MMAE_SHADOW_MSG);   // before the norm and the counters are touched
     int rc = mmae_sumsq(d->g, d->n, d->state, d->ws, stream);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -871,6 +883,7 @@ int mmae_opt_step_groups(const mmae_opt_groups_desc* d, void* stream) {
                  "opt_step_groups: n_groups out of range, or neither hyper nor hyper_dev given");
     MMAE_REQUIRE(((uintptr_t)d->p % 16 == 0) && ((uintptr_t)d->g % 16 == 0) && ((uintptr_t)d->m % 16 == 0) && ((uintptr_t)d->v % 16 == 0)
                  && ((uintptr_t)d->group_map % 2 == 0), "opt_step_groups: unaligned");
+    MMAE_REQUIRE(shadow_ok(d->shadow, d->shadow_dtype), "opt_step_groups" MMAE_SHADOW_MSG);
     int rc = mmae_sumsq(d->g, d->n, d->state, d->ws, stream);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;

@@ -898,6 +898,8 @@ int mmae_cast_f16_to_f32(const void* src, float* dst, int64_t n, const float* sc
 }
 int mmae_transpose_cast(const float* src, void* dst, int dst_dtype, int rows, int cols, void* stream) {
     MMAE_REQUIRE(src && dst && rows > 0 && cols > 0, "transpose_cast: bad argument");
+    // any other code used to take the f32 kernel and write 4-byte values into a 16-bit buffer
+    MMAE_REQUIRE(dst_dtype == MMAE_F32 || dst_dtype == MMAE_BF16, "transpose_cast: dst_dtype must be MMAE_F32 or MMAE_BF16");
     dim3 grid((cols + 63) / 64, (rows + 63) / 64), block(256);
     if (dst_dtype == MMAE_BF16) hipLaunchKernelGGL((transpose_cast_kernel<uint16_t>), grid, block, 0, (hipStream_t)stream, src, (uint16_t*)dst, rows, cols);
     else hipLaunchKernelGGL((transpose_cast_kernel<float>), grid, block, 0, (hipStream_t)stream, src, (float*)dst, rows, cols);

@@ -1395,6 +1395,15 @@ def patchify(img: Tensor, C: int, nh: int, nw: int, ph: int, pw: int, dtype: tor
 
 
 # ----------------------------------------------------------------------- optimiser --
+def _shadow_args(shadow: Optional[Tensor]):
+    """(pointer, dtype code) of the optimiser's shadow: the kernels write an f32 or a bf16 copy and nothing else (mmae.h, mmae_adamw)"""
+    if shadow is None:
+        return None, F32
+    if shadow.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'optimiser shadow must be float32 or bfloat16, got {shadow.dtype}')
+    return shadow.data_ptr(), dcode(shadow.dtype)
+
+
 def sumsq(x: Tensor, out: Tensor, ws: Tensor) -> None:
     check(_lib.load().mmae_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), _stream()), 'sumsq')
 
@@ -1404,15 +1413,13 @@ def adamw_dev(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, *, beta
     """AdamW with {lr, weight_decay, 1 - beta1^t, sqrt(1 - beta2^t)} read from the device tensor `hyper` (f32 [4])."""
     assert hyper.dtype == torch.float32 and hyper.numel() >= 4 and hyper.is_cuda
     check(_lib.load().mmae_adamw_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(), beta1, beta2,
-                                     eps, _p(grad_scale), _p(skip_flag), _p(shadow),
-                                     dcode(shadow.dtype) if shadow is not None else F32, _stream()), 'adamw_dev')
+                                     eps, _p(grad_scale), _p(skip_flag), *_shadow_args(shadow), _stream()), 'adamw_dev')
 
 
 def adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, *, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
           step: int, grad_scale: Optional[Tensor] = None, skip_flag: Optional[Tensor] = None, shadow: Optional[Tensor] = None) -> None:
     check(_lib.load().mmae_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,
-                                 weight_decay, step, _p(grad_scale), _p(skip_flag), _p(shadow),
-                                 dcode(shadow.dtype) if shadow is not None else F32, _stream()), 'adamw')
+                                 weight_decay, step, _p(grad_scale), _p(skip_flag), *_shadow_args(shadow), _stream()), 'adamw')
 
 
 def opt_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, istate: Tensor, ws: Tensor, *, lr: float, weight_decay: float,
@@ -1424,7 +1431,7 @@ def opt_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, istate: 
     counted on its own, istate[4]; the loss scale still on the gradients, folded into the step's multiply)."""
     d = OptDesc()
     d.p, d.g, d.m, d.v, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-    d.shadow, d.shadow_dtype = _p(shadow), (dcode(shadow.dtype) if shadow is not None else F32)
+    d.shadow, d.shadow_dtype = _shadow_args(shadow)
     d.lr, d.weight_decay, d.beta1, d.beta2, d.eps = lr, weight_decay, beta1, beta2, eps
     d.lrwd_dev, d.loss_dev = _p(lrwd_dev), _p(loss_dev)
     d.found_inf_dev, d.grad_scale_dev = _p(found_inf_dev), _p(grad_scale_dev)
@@ -1448,7 +1455,7 @@ def opt_step_groups(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, i
     assert state.dtype == torch.float32 and state.numel() >= 8 and istate.dtype == torch.int32 and istate.numel() >= 8
     d = OptGroupsDesc()
     d.p, d.g, d.m, d.v, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n
-    d.shadow, d.shadow_dtype = _p(shadow), (dcode(shadow.dtype) if shadow is not None else F32)
+    d.shadow, d.shadow_dtype = _shadow_args(shadow)
     d.beta1, d.beta2, d.eps = beta1, beta2, eps
     d.clip_grad, d.skip_grad, d.grad_prescale = (clip_grad or 0.0), (skip_grad or 0.0), grad_prescale
     d.loss_dev, d.found_inf_dev, d.grad_scale_dev = _p(loss_dev), _p(found_inf_dev), _p(grad_scale_dev)

@@ -1,5 +1,6 @@
 """Shared test helpers: golden loading, model builders for the engine and the oracle config."""
 import json
+import math
 import os
 
 import numpy as np
@@ -422,3 +423,226 @@ def ce_loss_ref(logits, target, mask, P: int, eps: float, up: float = 1.0, n_res
     dp = pr * (torch.expm1(b_lse[:, None] + U32 * (l - lse[:, None]).abs()) + 2 * U32)
     bg = (wc.abs() * (dp + U32 * (pr - y).abs() + U32) + 5 * U32 * g.abs()) * use[:, None]
     return dict(lse=(lse, b_lse), sum=(s, bs), cnt=cnt, loss=(loss, bl), nvalid=nvalid, g=g, bg=bg, w=w, mi=mi)
+
+
+# ----------------------------------------------------------------------------------------------
+# Optimiser (losses.hip: sumsq_stage1/2, opt_finalize_kernel, adamw_kernel, adamw_groups_kernel), streaming casts (rowops.hip,
+# gemm_f32x3.hip: x3_split) and the truncated depth standardisation (depth.hip).  The library is built without fast-math:
+# sqrtf and `/` are the correctly rounded forms (one rounding each, u = 2^-24), products and sums may contract to FMAs
+# (fewer roundings, never more).  Every product can also leave the normal range: hardware may flush the result or keep it
+# subnormal, either way it moves by at most one f32 minimum normal, TINY32, which the bounds add per product as an absolute floor.
+TINY32 = 2.0 ** -126
+
+
+def f32r(x) -> float:
+    """a Python float rounded to f32 (what a `float` argument of the C ABI carries)"""
+    return float(np.float32(x))
+
+
+def bias_corrections(b1: float, b2: float, t: int):
+    """(float)(1 - b1^t), (float)sqrt(1 - b2^t) formed in double from the f32 betas, as mmae_adamw / opt_finalize_kernel do"""
+    b1, b2 = f32r(b1), f32r(b2)
+    return f32r(1.0 - b1 ** t), f32r(math.sqrt(1.0 - b2 ** t))
+
+
+def _h(x, dev):
+    """a hyper-parameter as the kernel receives it -- rounded to f32 -- widened to fp64 (a scalar, or one value per element)"""
+    return torch.as_tensor(x, dtype=torch.float64).to(torch.float32).to(device=dev, dtype=torch.float64)
+
+
+def adamw_ref(p, g, m, v, *, lr, wd, b1, b2, eps, bc1, bc2_sqrt, gs=1.0):
+    """One AdamW step of adamw_kernel / adamw_groups_kernel in fp64 on the f32 operands and the f32-rounded hyper-parameters the
+    kernel receives (lr, wd: scalars or one value per element).  Returns (p', bound), (m', bound), (v', bound).  Rounding points of
+        gj = g gs;  m' = b1 m + (1 - b1) gj;  v' = b2 v + (1 - b2) gj gj;  den = sqrtf(v') / bc2_sqrt + eps;
+        p' = p (1 - lr wd) - (lr / bc1) (m' / den)
+    counted along each term (the two paths of each kernel contract differently, each to fewer roundings than counted here):
+      m'   b1 m: product, sum = 2;  (1 - b1) gj: 1 - b1, gj, product, sum = 4.  The terms can cancel, so each is bounded on its
+           own magnitude: gamma_2 |b1 m| + gamma_4 |(1 - b1) g gs|, + 3 TINY32 (three products)
+      v'   b2 v: 2;  (1 - b2) gj gj: 1 - b2, gj twice, two products, sum = 6; all terms non-negative: gamma_2 b2 v + gamma_6 (..),
+           + 4 TINY32 (gj^2 leaves the normal range below |gj| ~ 1e-19)
+      den  sqrt moves by |dv| / (sqrt v' + sqrt v^) <= min(dv / sqrt v', sqrt dv), + u sqrt v' (sqrtf); / bc2_sqrt and + eps round
+           values <= den: gamma_2 den
+      step (lr / bc1) m' / den: lr / bc1, the division by den and the product round once each (gamma_3 |step|); m' and den enter
+           to first order as (lr / bc1) dm / den and |step| dden / den, their cross term through the factor 1 / (1 - dden / den)
+      p'   lr wd and 1 - lr wd round once each: |ddecay| <= u (|lr wd| + |1 - lr wd|); p decay rounds once; the difference once:
+           |p| ddecay + u |p decay| + dstep + u |p'| (the last two roundings taken at the perturbed values)"""
+    dev = p.device
+    P, G, M, V = (t.detach().double() for t in (p, g, m, v))
+    lr, wd, b1, b2, eps, bc1, bc2, gs = (_h(x, dev) for x in (lr, wd, b1, b2, eps, bc1, bc2_sqrt, gs))
+    gj = G * gs
+    t1, t2 = b1 * M, (1 - b1) * gj
+    m2 = t1 + t2
+    b_m = gamma(2) * t1.abs() + gamma(4) * t2.abs() + 3 * TINY32
+    w1, w2 = b2 * V, (1 - b2) * gj * gj
+    v2 = w1 + w2
+    b_v = gamma(2) * w1.abs() + gamma(6) * w2 + 4 * TINY32
+    sv = v2.clamp_min(0).sqrt()
+    b_s = torch.minimum(b_v / sv.clamp_min(1e-300), b_v.sqrt()) + U32 * sv
+    den = sv / bc2 + eps
+    b_den = (b_s / bc2) * (1 + gamma(2)) + gamma(2) * den
+    c = lr / bc1
+    step = c * m2 / den
+    r_den = b_den / den
+    b_step = (c.abs() / den * b_m + step.abs() * r_den) / (1 - r_den)
+    b_step = b_step + gamma(3) * (step.abs() + b_step) + 2 * TINY32
+    lw = lr * wd
+    dec = 1 - lw
+    b_dec = U32 * (lw.abs() + dec.abs()) * (1 + U32)
+    pd = P * dec
+    b_pd = P.abs() * b_dec
+    b_pd = b_pd + U32 * (pd.abs() + b_pd) + TINY32
+    p2 = pd - step
+    b_p = b_pd + b_step
+    b_p = b_p + U32 * (p2.abs() + b_p)
+    return (p2, b_p), (m2, b_m), (v2, b_v)
+
+
+def sumsq_chain(n: int) -> int:
+    """Longest chain of fp32 roundings a term of mmae_sumsq's sum passes.  sumsq_stage1 runs nb = min(ceil(n / 1024), 1024)
+    workgroups of 256 lanes, a lane takes 4 elements per trip and T = ceil(n / (1024 nb)) trips: a term of its first trip is
+    squared (1), summed in its pair (1) and with the other pair (1), added to the lane's sum (1), then moved once by each of the
+    T - 1 later additions; the lane whose last trip is the scalar tail adds up to 3 terms one by one instead of one quad (+2):
+    T + 5.  block_sum2: 6 wave shuffles + 2 additions of the four wave sums = 8.  sumsq_stage2: a lane adds at most
+    ceil(1024 / 256) = 4 partials, then the same block reduction: 4 + 8.  L = T + 25."""
+    nb = min((n + 1023) // 1024, 1024)
+    T = (n + 1024 * nb - 1) // (1024 * nb)
+    return T + 25
+
+
+def sumsq_ref(x):
+    """sum x^2 in fp64 and its bound gamma_L sum x^2 (every term non-negative, so the relative bound of the longest chain holds
+    for the sum), + n TINY32 for squares that leave the normal range.  A non-finite x gives a non-finite sum and bound."""
+    X = x.detach().double().reshape(-1)
+    s = float((X * X).sum())
+    return s, gamma(sumsq_chain(X.numel())) * s + X.numel() * TINY32
+
+
+def opt_decision_ref(ss: float, b_ss: float, *, istate, lr, wd, b1, b2, clip, skip_at, prescale, lrwd=None, loss=None,
+                     found_inf=None, grad_scale=None):
+    """The decisions of opt_finalize_kernel (mmae.h, mmae_opt_step) restated: ss, b_ss the gradient's sum of squares and its bound
+    (sumsq_ref), istate the six counters before the step, every other argument as in mmae_opt_desc (None / 0: not given).
+    Returns the expected state[1..6] -- norm and scale as (value, bound), lr, wd and the two bias corrections as f32 values -- the
+    expected istate[0..5] and `skip`.
+      pre    = grad_prescale / grad_scale                       one division
+      norm   = sqrtf(ss) pre: sqrt halves ss's relative error, sqrtf and the product round once each, pre carries one:
+               relative b_ss / (2 ss) + gamma_3
+      scale  = pre min(1, clip / (norm + 1e-6f)): norm's error, then 1e-6f, the sum, the division and the product (gamma_4), + pre's;
+               min(1, .) is 1-Lipschitz, so the bound holds on either side of the switch.  Without clip: pre alone (u)
+    A test keeps skip_at away from norm by more than norm's bound; the integers are exact."""
+    clip, skip_at = float(clip or 0.0), float(skip_at or 0.0)
+    pre = f32r(prescale)
+    if grad_scale is not None:
+        pre = pre / f32r(grad_scale)
+    norm = math.sqrt(ss) * pre if ss >= 0 else float('nan')
+    fin = math.isfinite(norm)
+    r_norm = (b_ss / (2 * ss) if fin and ss > 0 else 0.0) + gamma(3)
+    loss_bad = loss is not None and not math.isfinite(loss)
+    amp_bad = found_inf is not None and found_inf > 0
+    skip = (not fin) or (clip <= 0 and skip_at > 0 and norm >= skip_at) or loss_bad or amp_bad
+    scale, r_scale = pre, U32
+    if clip > 0:
+        cc = f32r(clip) / (norm + 1e-6) if not math.isnan(norm) else float('nan')
+        scale *= cc if cc < 1 else 1.0                 # a NaN norm leaves pre, an infinite one gives 0 -- as the kernel's comparison does
+        r_scale = r_norm + gamma(4) + U32
+    t = int(istate[1]) + (0 if skip else 1)
+    ist = [1 if skip else 0, t, int(istate[2]) + loss_bad, int(istate[3]) + skip, int(istate[4]) + amp_bad, int(istate[5]) + (not fin)]
+    bc1, bc2 = bias_corrections(b1, b2, max(t, 1))
+    lr_, wd_ = (lrwd[0], lrwd[1]) if lrwd is not None else (lr, wd)
+    b_norm = r_norm * norm if fin else float('nan')
+    return dict(state={1: (norm, b_norm), 2: (scale, r_scale * abs(scale) if math.isfinite(scale) else float('nan')),
+                       3: f32r(lr_), 4: f32r(wd_), 5: bc1, 6: bc2}, istate=[int(x) for x in ist], skip=bool(skip))
+
+
+def depth_std_ref(x, lo: int, hi: int, eps: float):
+    """Truncated standardisation of x [B, n] in fp64: stable sort, slice [lo, hi), mean, unbiased variance, (x - mean) /
+    sqrt(var + eps) (eps as the f32 the kernel receives), with the bound of depth_standardize_kernel's last line
+        y = (x - (float)mean) * (1.0f / sqrtf((float)var + eps))
+      absolute  rs u |mean|: the mean rounded to f32 shifts every element by as much -- what is left where x ~ mean
+      relative  rs: (float)var and + eps round once each, the root halves them (u), sqrtf and the reciprocal round once each: 3u;
+                the difference and the product once each: gamma_5 |y|, taken at the shifted value
+    The kernel's sums are fp64 over at most n terms (relative n 2^-53 on the mean of the magnitudes, and on var by the two-pass
+    form), folded in as n 2^-52 on both parts."""
+    X = x.detach().double()
+    n = X.shape[-1]
+    s = torch.sort(X, dim=-1, stable=True).values[..., lo:hi]
+    mean = s.mean(-1, keepdim=True)
+    var = s.var(-1, unbiased=True, keepdim=True)
+    e = float(_h(eps, 'cpu'))
+    rs = 1.0 / torch.sqrt(var + e)
+    y = (X - mean) * rs
+    d64 = n * 2.0 ** -52
+    a = rs * (U32 * mean.abs() + d64 * s.abs().mean(-1, keepdim=True))
+    return y, a * (1 + gamma(5)) + (gamma(5) + d64) * y.abs()
+
+
+# ---- bit-exact restatements (torch on the CPU; integer arithmetic wherever the header fixes the bits) --------------------------
+def _i16(r):
+    """integers 0 .. 65535 (int64) -> the int16 tensor with those bits"""
+    return torch.where(r >= 32768, r - 65536, r).to(torch.int16)
+
+
+def bf16_bits_ref(x):
+    """common.h's f32_to_bf16_bits on an f32 tensor: round to nearest even on the integer image (a value at or above 0x7f7f8000
+    carries into the exponent: inf), a NaN keeps its top 16 bits with the quiet bit set.  Returns int16 bit patterns."""
+    u = x.detach().contiguous().view(torch.int32).to(torch.int64) & 0xffffffff       # integer arithmetic: the same on any device
+    nan = (u & 0x7fffffff) > 0x7f800000
+    r = ((u + 0x7fff + ((u >> 16) & 1)) >> 16) & 0xffff
+    return _i16(torch.where(nan, ((u >> 16) | 0x40) & 0xffff, r))
+
+
+def bf16_to_f32_ref(bits):
+    """bf16_bits_to_f32: the 16 bits (int16 or bfloat16 tensor) become the top half of an f32, NaN payloads included"""
+    return (bits.detach().contiguous().view(torch.int16).to(torch.int32) << 16).view(torch.float32)
+
+
+def h16_scale_ref(amax):
+    """(S, 1 / S) of mmae.h's MMAE_F16 gradient scale, S = 2^(4 - floor(log2 m)), from the formula; S = 1 without the scalar, for
+    m = 0, a subnormal, inf, NaN, and outside 2^-119 <= m < 2^127 (the range common.h's h16_grad_scale applies the formula in)."""
+    if amax is None:
+        return 1.0, 1.0
+    m = abs(f32r(amax))
+    if not (math.isfinite(m) and 2.0 ** -119 <= m < 2.0 ** 127):
+        return 1.0, 1.0
+    k = 4 - (math.frexp(m)[1] - 1)                     # frexp: m = f 2^e with 0.5 <= f < 1, so floor(log2 m) = e - 1
+    return 2.0 ** k, 2.0 ** -k
+
+
+def f32_to_f16_ref(x, amax=None):
+    """cast_f16_kernel<true>: the f32 product x S (S a power of two: exact unless it leaves f32's range), then IEEE round to
+    nearest even into fp16 -- beyond 65520 to inf, never clamped"""
+    return (x.detach().cpu().float() * h16_scale_ref(amax)[0]).to(torch.float16)
+
+
+def f16_to_f32_ref(h, amax=None):
+    """cast_f16_kernel<false>: the exact fp16 -> f32 conversion times 1 / S, rounded to f32"""
+    return h.detach().cpu().to(torch.float32) * h16_scale_ref(amax)[1]
+
+
+def fma_f32_ref(a, x, y):
+    """fmaf(a, x, y) element-wise on f32 tensors, correctly rounded: a x is exact in fp64 (48 bits); the fp64 sum with y is made
+    round-to-odd -- when TwoSum leaves a remainder and the sum's last bit is even, step one fp64 towards the remainder -- and
+    rounding that to f32 cannot double-round (53 >= 2 * 24 + 2 bits)."""
+    ax = torch.as_tensor(a, dtype=torch.float32).double() * x.detach().cpu().double()
+    yd = y.detach().cpu().double()
+    s = ax + yd
+    bb = s - ax
+    e = (ax - (s - bb)) + (yd - bb)                    # TwoSum: ax + y = s + e exactly
+    even = (s.view(torch.int64) & 1) == 0
+    toward = torch.where(e > 0, torch.full_like(s, float('inf')), torch.full_like(s, float('-inf')))
+    s = torch.where((e != 0) & even & torch.isfinite(s), torch.nextafter(s, toward), s)
+    return s.to(torch.float32)
+
+
+def add_n_ref(xs):
+    """add_n_kernel: the left-to-right chain ((in0 + in1) + in2) + ... in f32"""
+    s = xs[0].detach().cpu().float().clone()
+    for t in xs[1:]:
+        s = s + t.detach().cpu().float()
+    return s
+
+
+def x3_split_ref(x):
+    """split8 on finite f32 values: hi = bf16(x), lo = bf16(x - hi) (the difference is exact in f32).  Returns int16 bits (hi, lo)."""
+    x = x.detach().cpu().float()
+    hi = bf16_bits_ref(x)
+    return hi, bf16_bits_ref(x - bf16_to_f32_ref(hi))

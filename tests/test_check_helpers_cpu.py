@@ -228,3 +228,234 @@ def test_ce_lse_of_one_pixel_off_and_an_ignored_target_read_are_flagged():
     g[0, 0, y, x] -= ref['w'][0] * 0.9
     with pytest.raises(AssertionError, match='outside the bound'):
         assert_within(g.float(), ref['g'], ref['bg'], 'CE gradient at an ignored pixel')
+
+
+# ---- optimiser, cast and depth references (adamw_ref, sumsq_ref, opt_decision_ref, depth_std_ref, the bit-exact restatements) ----
+from helpers import (TINY32, adamw_ref, add_n_ref, bf16_bits_ref, bf16_to_f32_ref, bias_corrections, depth_std_ref, f16_to_f32_ref,  # noqa: E402
+                     f32_to_f16_ref, f32r, fma_f32_ref, h16_scale_ref, opt_decision_ref, sumsq_chain, sumsq_ref, x3_split_ref)
+
+_HY = dict(lr=1e-3, wd=0.05, b1=0.9, b2=0.95, eps=1e-8)
+
+
+def _adamw_f32(p, g, m, v, *, lr, wd, b1, b2, eps, bc1, bc2_sqrt, gs=1.0):
+    """adamw_kernel's expressions in plain f32 on the CPU, one rounding per operation (no FMA contraction)"""
+    t = lambda x: torch.as_tensor(x, dtype=torch.float64).to(torch.float32)
+    lr, wd, b1, b2, eps, bc1, bc2, gs = (t(x) for x in (lr, wd, b1, b2, eps, bc1, bc2_sqrt, gs))
+    gj = g * gs
+    m2 = b1 * m + (1 - b1) * gj
+    v2 = b2 * v + (1 - b2) * gj * gj
+    p2 = p * (1 - lr * wd) - (lr / bc1) * (m2 / (v2.sqrt() / bc2 + eps))
+    return p2, m2, v2
+
+
+def _opt_operands(mix, n=100003, seed=11):
+    g_ = torch.Generator().manual_seed(seed)
+    p, g, m = torch.randn(n, generator=g_), torch.randn(n, generator=g_), torch.randn(n, generator=g_) * 0.1
+    v = torch.rand(n, generator=g_) * 0.01
+    if mix == 'cancel':                                  # m' = b1 m + (1 - b1) g cancels to ~1e-6 of its terms
+        m = -(1 - f32r(0.9)) / f32r(0.9) * g * (1 + 1e-6 * torch.randn(n, generator=g_))
+    elif mix == 'zero':                                  # the denominator is eps
+        g, v = torch.zeros(n), torch.zeros(n)
+    elif mix == 'tiny':                                  # gj^2 below the normal range
+        g, m, v = g * 1e-20, m * 1e-20, v * 1e-40
+    elif mix == 'huge':
+        g = g * 1e15
+    return p, g, m, v
+
+
+@pytest.mark.parametrize('t', [1, 3, 1000])
+@pytest.mark.parametrize('mix', ['random', 'cancel', 'zero', 'tiny', 'huge'])
+def test_adamw_ref_passes_a_plain_f32_restatement(mix, t):
+    p, g, m, v = _opt_operands(mix)
+    bc1, bc2 = bias_corrections(0.9, 0.95, t)
+    for gs in (1.0, 0.37):
+        kw = dict(_HY, bc1=bc1, bc2_sqrt=bc2, gs=gs)
+        for name, o, (r, b) in zip('pmv', _adamw_f32(p, g, m, v, **kw), adamw_ref(p, g, m, v, **kw)):
+            assert_within(o, r, b, f"{name}' ({mix}, t = {t}, gs = {gs})")
+
+
+def _old_opt_criterion(p_bad, v_bad, p_ref, v_ref):
+    """test_adamw_and_sumsq's: rel-L2 < 1e-6 on p and v (m was not compared)"""
+    return rel_err(p_bad, p_ref) < 1e-6 and rel_err(v_bad, v_ref) < 1e-6
+
+
+# (corruption, does the old rel-L2 criterion pass it?)
+@pytest.mark.parametrize('corruption,old_passes', [('tail element not updated', False), ('chunk with the neighbour group\'s weight decay', False),
+                                                   ('bias corrections of t + 1', False), ('m not written', True)])
+def test_optimiser_corruptions_are_flagged(corruption, old_passes):
+    p, g, m, v = _opt_operands('random')
+    t = 3
+    bc1, bc2 = bias_corrections(0.9, 0.95, t)
+    kw = dict(_HY, bc1=bc1, bc2_sqrt=bc2)
+    (pr, bp), (mr, bm), (vr, bv) = adamw_ref(p, g, m, v, **kw)
+    pb, mb, vb = (x.clone() for x in _adamw_f32(p, g, m, v, **kw))
+    if corruption == 'tail element not updated':         # the last element of the scalar tail (n % 4 = 3)
+        pb[-1], mb[-1], vb[-1] = p[-1], m[-1], v[-1]
+    elif corruption.startswith('chunk'):                 # one 64-element chunk decayed with wd = 0 (the no-decay group next to it)
+        c = slice(64 * 700, 64 * 701)
+        pb[c] = _adamw_f32(p[c], g[c], m[c], v[c], **dict(kw, wd=0.0))[0]
+    elif corruption.startswith('bias'):
+        b1n, b2n = bias_corrections(0.9, 0.95, t + 1)
+        pb = _adamw_f32(p, g, m, v, **dict(kw, bc1=b1n, bc2_sqrt=b2n))[0]
+    else:
+        mb = m.clone()
+    assert _old_opt_criterion(pb, vb, pr, vr) == old_passes
+    with pytest.raises(AssertionError, match='outside the bound'):
+        assert_within(pb, pr, bp, 'p')
+        assert_within(mb, mr, bm, 'm')
+        assert_within(vb, vr, bv, 'v')
+
+
+def test_truncated_shadow_is_flagged_by_the_bit_comparison():
+    p = _opt_operands('random')[0]
+    good = bf16_bits_ref(p)
+    assert torch.equal(good, p.bfloat16().view(torch.int16))          # finite values: torch's own rounding
+    trunc = (p.view(torch.int32) >> 16).to(torch.int16)
+    n_bad = int((trunc != good).sum())
+    assert 0.4 * p.numel() < n_bad < 0.6 * p.numel()                  # half of all values round up
+    # the old check, torch.equal with p.bfloat16(), catches this one too; rel-L2 at the bf16 tolerance 4e-3 would not
+    assert rel_err(bf16_to_f32_ref(trunc), p) < 4e-3
+
+
+def test_sumsq_ref_and_chain():
+    assert sumsq_chain(1) == 26 and sumsq_chain(1048576) == 26 and sumsq_chain(1048577) == 27 and sumsq_chain(3 * 1048576) == 28
+    g_ = torch.Generator().manual_seed(12)
+    for n in (1, 5, 100003, 2 * 1048576 + 1027):
+        x = torch.randn(n, generator=g_)
+        s, b = sumsq_ref(x)
+        assert abs(float((x * x).sum()) - s) <= b                      # f32 products, torch's cascaded f32 sum
+        assert abs(float((x * x).sum()) * (1 + 3e-6) - s) > b          # a sum 3e-6 off is outside gamma_26 = 1.6e-6
+    x = torch.full((4096,), 1e-3)
+    x[1234] = 3.0                                                      # one large element among tiny ones
+    s, b = sumsq_ref(x)
+    assert abs(9.0 - s) > b and abs(float((x * x).sum()) - s) <= b     # dropping the tiny ones is flagged
+
+
+def test_opt_decision_ref_rules():
+    kw = dict(lr=1e-3, wd=0.05, b1=0.9, b2=0.95)
+    z = [0] * 6
+    r = opt_decision_ref(4.0, 0.0, istate=z, clip=1.0, skip_at=1.5, prescale=1.0, **kw)          # clip before skip_grad: exclusive
+    assert r['istate'] == [0, 1, 0, 0, 0, 0] and not r['skip'] and r['state'][1][0] == 2.0
+    assert r['state'][2][0] == pytest.approx(1.0 / (2.0 + 1e-6)) and r['state'][5] == f32r(1 - f32r(0.9))
+    r = opt_decision_ref(4.0, 0.0, istate=[0, 7, 1, 2, 3, 4], clip=0.0, skip_at=1.5, prescale=1.0, **kw)
+    assert r['istate'] == [1, 7, 1, 3, 3, 4] and r['state'][2][0] == 1.0                          # t stays put
+    assert (r['state'][5], r['state'][6]) == bias_corrections(0.9, 0.95, 7)
+    r = opt_decision_ref(4.0 * 65536 ** 2, 0.0, istate=z, clip=0.0, skip_at=0.0, prescale=0.5, grad_scale=65536.0, **kw)
+    assert r['state'][1][0] == 1.0 and r['state'][2][0] == 0.5 / 65536 and r['istate'][:2] == [0, 1]
+    r = opt_decision_ref(4.0, 0.0, istate=z, clip=0.0, skip_at=0.0, prescale=1.0, found_inf=1.0, loss=float('inf'), **kw)
+    assert r['istate'] == [1, 0, 1, 1, 1, 0]
+    r = opt_decision_ref(float('nan'), float('nan'), istate=z, clip=1.0, skip_at=0.0, prescale=1.0, lrwd=(0.5, 0.25), **kw)
+    assert r['istate'] == [1, 0, 0, 1, 0, 1] and r['state'][2][0] == 1.0 and (r['state'][3], r['state'][4]) == (0.5, 0.25)
+    r = opt_decision_ref(float('inf'), float('nan'), istate=z, clip=1.0, skip_at=0.0, prescale=1.0, **kw)
+    assert r['istate'] == [1, 0, 0, 1, 0, 1] and r['state'][2][0] == 0.0
+
+
+# ---- depth --------------------------------------------------------------------------------------------------------------------
+def _depth_f32(x, lo, hi, eps):
+    """the kernel's arithmetic on the CPU: fp64 statistics of the sorted slice, the last line in f32"""
+    s = torch.sort(x.double(), dim=-1).values[..., lo:hi]
+    mu = s.mean(-1, keepdim=True).float()
+    var = s.var(-1, unbiased=True, keepdim=True).float()
+    return (x - mu) * (1.0 / torch.sqrt(var + torch.tensor(eps, dtype=torch.float32)))
+
+
+def _depth_maps(n=1000, seed=13):
+    g_ = torch.Generator().manual_seed(seed)
+    ties = torch.randint(0, 7, (n,), generator=g_).float() * 0.25 - 0.5          # seven values, long runs: every cut is inside one
+    return torch.stack([torch.randn(n, generator=g_) * 3 + 10, -torch.rand(n, generator=g_) * 5 - 1, ties,
+                        torch.full((n,), 2.5), (torch.arange(n) % 2).float() * 4 - 1])
+
+
+@pytest.mark.parametrize('lohi', [(0, 1000), (0, 2), (998, 1000), (100, 900), (499, 501)])
+def test_depth_std_ref_passes_a_plain_f32_restatement(lohi):
+    x = _depth_maps()
+    y, b = depth_std_ref(x, *lohi, 1e-6)
+    assert_within(_depth_f32(x, *lohi, 1e-6), y, b, f'depth standardisation, cuts {lohi}', names=('b', 'i'))
+
+
+def _old_depth_criterion(bad, ref):
+    """test_depth_standardize's: max |difference| < 2e-6 max |reference| + 1e-6"""
+    return float((bad.double() - ref).abs().max()) < 2e-6 * float(ref.abs().max()) + 1e-6
+
+
+@pytest.mark.parametrize('corruption,old_passes', [('cut value counted once', False), ('biased variance', False), ('lo + 1', False)])
+def test_depth_corruptions_are_flagged(corruption, old_passes):
+    x = _depth_maps()[2:3]                                # the map with long runs of ties
+    lo, hi = 100, 900
+    y, b = depth_std_ref(x, lo, hi, 1e-6)
+    s = torch.sort(x.double(), dim=-1).values
+    if corruption == 'cut value counted once':            # values strictly between the cuts, each cut value once
+        k1, k2 = s[0, lo], s[0, hi - 1]
+        sl = torch.cat([s[0][(s[0] > k1) & (s[0] < k2)], k1[None], k2[None]])[None]
+    elif corruption == 'biased variance':
+        sl = s[:, lo:hi]
+    else:
+        sl = s[:, lo + 1:hi]
+    mu, var = sl.mean(-1, keepdim=True), sl.var(-1, unbiased=corruption != 'biased variance', keepdim=True)
+    bad = ((x.double() - mu) / torch.sqrt(var + 1e-6)).float()
+    assert _old_depth_criterion(bad, y) == old_passes
+    with pytest.raises(AssertionError, match='outside the bound'):
+        assert_within(bad, y, b, corruption)
+
+
+# ---- bit-exact restatements ----------------------------------------------------------------------------------------------------
+def _f(bits):
+    """f32 values from their bit patterns"""
+    return torch.tensor([b - (1 << 32) if b >= (1 << 31) else b for b in bits], dtype=torch.int32).view(torch.float32)
+
+
+def test_bf16_restatement_known_answers():
+    x = _f([0x3f800000, 0x3f808000, 0x3f818000, 0x3f808001, 0x7f7f8000, 0x7f7f7fff, 0xff7f8000, 0x7f800000, 0x7fa00001, 0xffc12345,
+            0x00000000, 0x80000000, 0x00008000, 0x00018000, 0x00000001])
+    want = [0x3f80, 0x3f80, 0x3f82, 0x3f81, 0x7f80, 0x7f7f, 0xff80, 0x7f80, 0x7fe0, 0xffc1, 0x0000, 0x8000, 0x0000, 0x0002, 0x0000]
+    got = [int(b) & 0xffff for b in bf16_bits_ref(x)]
+    assert got == want                                   # ties to even both ways, the carry into inf, quieted NaN, subnormals
+    back = bf16_to_f32_ref(bf16_bits_ref(x))
+    assert [int(b) & 0xffffffff for b in back.view(torch.int32)] == [w << 16 for w in want]
+    g_ = torch.Generator().manual_seed(14)
+    r = torch.randn(100003, generator=g_) * 1e3
+    assert torch.equal(bf16_bits_ref(r), r.bfloat16().view(torch.int16))
+    hi, lo = x3_split_ref(r)
+    rec = bf16_to_f32_ref(hi).double() + bf16_to_f32_ref(lo).double()
+    assert bool(((rec - r.double()).abs() <= r.double().abs() * 2.0 ** -16).all())       # hi + lo keeps 16 bits of x
+
+
+def test_h16_scale_restatement():
+    assert h16_scale_ref(None) == (1.0, 1.0)
+    for m in (0.0, 1e-45, 2.0 ** -127, float('inf'), float('nan'), 2.0 ** -120, 2.0 ** -119 * (1 - 2.0 ** -24), 2.0 ** 127, 3e38):
+        assert h16_scale_ref(m) == (1.0, 1.0), m
+    for k in (-119, -60, 0, 5, 126):
+        for f in (1.0, 1.5, 1.999):
+            assert h16_scale_ref(2.0 ** k * f) == (2.0 ** (4 - k), 2.0 ** (k - 4))
+    assert h16_scale_ref(0.9e-6)[0] == 2.0 ** 25                      # test_h16_gpu's value: 2^-21 <= 0.9e-6 < 2^-20
+    x = torch.tensor([65504.0, 65519.996, 65520.0, -65520.0, 1e5, 2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * 1.0001, 6e-8, float('nan')])
+    h = f32_to_f16_ref(x)
+    assert h[:9].tolist() == [65504.0, 65504.0, float('inf'), float('-inf'), float('inf'), 2.0 ** -24, 0.0, 2.0 ** -24, 2.0 ** -24]
+    assert bool(torch.isnan(h[9]))
+    assert f16_to_f32_ref(f32_to_f16_ref(torch.tensor([3e-5]), 2e-5), 2e-5).item() == pytest.approx(3e-5, rel=2.0 ** -11)
+
+
+def test_fma_and_add_n_restatements():
+    g_ = torch.Generator().manual_seed(15)
+    x, y = torch.randn(200003, generator=g_), torch.randn(200003, generator=g_)
+    a = 0.3
+    f = fma_f32_ref(a, x, y)
+    exact = torch.tensor(a, dtype=torch.float32).double() * x.double() + y.double()
+    assert bool(((f.double() - exact).abs() <= 0.5 * ulp(torch.float32, exact) * (1 + 1e-9)).all())   # correctly rounded
+    two = y + torch.tensor(a, dtype=torch.float32) * x
+    assert 0 < int((two != f).sum()) < 0.2 * x.numel()                # mul + add differs from the FMA in some elements
+    # a tie the fp64 sum alone would double-round: a x = 2^-30 exactly behind a half-ulp of y = 1
+    assert float(fma_f32_ref(2.0 ** -15, torch.tensor([2.0 ** -15 + 2.0 ** -38]), torch.tensor([1.0 + 2.0 ** -24 - 2.0 ** -30]))) >= 1.0
+    xs = [torch.randn(4096, generator=g_) * 10 ** k for k in range(4)]
+    assert torch.equal(add_n_ref(xs), ((xs[0] + xs[1]) + xs[2]) + xs[3])
+
+
+def test_ops_refuses_a_shadow_dtype_the_optimiser_kernels_do_not_write():
+    from multimae_amd import ops
+    assert ops._shadow_args(None) == (None, 0)
+    for dt, code in ((torch.float32, 0), (torch.bfloat16, 1)):
+        t = torch.zeros(8, dtype=dt)
+        assert ops._shadow_args(t) == (t.data_ptr(), code)
+    for dt in (torch.float16, torch.float64, torch.int16):
+        with pytest.raises(TypeError, match='float32 or bfloat16'):
+            ops._shadow_args(torch.zeros(8, dtype=dt))
