@@ -347,6 +347,7 @@ int mmae_colsum_batch(const mmae_colsum_job* jobs, int n, int accumulate, float*
  * f32 parity mode).  Replaces attn.softmax(dim=-1), multimae_utils.py:176,207.
  *   fwd: P[r][0:n] = softmax(scale * S[r][0:n]); P[r][n:ldp] = 0.  S f32, P act dtype.
  *   bwd: dS = scale * P .* (dP - sum_j dP_j P_j); dS[r][n:ld] = 0.  dP f32, dS act dtype.
+ * Any row length: rows with ld <= 256 are held in registers (one wave per row), longer ones are walked in passes.
  * ------------------------------------------------------------------------- */
 int mmae_softmax_fwd(const float* S, int64_t lds_, void* P, int p_dtype, int64_t ldp, int64_t rows, int n,
                      float scale, void* stream);
@@ -405,6 +406,25 @@ int mmae_attn_bwd_f16(const void* q, const void* k, const void* v, const void* o
                       void* dv, int B, int H, int Nq, int Nk, int hd, int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb,
                       int64_t v_sr, int64_t o_sb, int64_t o_sr, int64_t dq_sb, int64_t dq_sr, int64_t dk_sb, int64_t dk_sr, int64_t dv_sb,
                       int64_t dv_sr, float scale, void* stream);
+/* Tiled ("flash-style") bf16 attention for sequences of any length: head_dim 32 or 64, 1 <= Nq, Nk, self- or cross-attention (Nq != Nk
+ * allowed, either side may be <= 256).  Replaces the same reference lines as mmae_attn_fwd / mmae_attn_bwd (multimae_utils.py:175-179,
+ * 206-210, and their autograd) where a head's K and V no longer fit LDS: one workgroup per (128-query block, batch * head), K and V
+ * streamed through LDS in double-buffered 128-key tiles with the online-softmax rescale; nothing of size Nq * Nk is ever stored.  Same
+ * operand addressing (base + b*s_b + row*s_r + h*head_dim, strides multiples of 8 elements, q / k / v may be column slices of a packed
+ * qkv / kv activation) and the same lse (f32 [B][H][Nq] = max + log(sum) of the scaled scores) as mmae_attn_fwd.
+ * Backward = two launches with no sum across workgroups and no atomics (bit-reproducible): the dq kernel (one workgroup per query block)
+ * first writes delta, f32 scratch [B][H][Nq], delta_i = sum_j P_ij dP_ij formed from the kernel's own fp32 P and dP (not rowsum(dO . O)
+ * of the stored bf16 O, see above), then dS and dq; the dk / dv kernel (one workgroup per key block) reads lse and delta.  delta's
+ * contents on entry do not matter; o is not read (kept for symmetry with mmae_attn_bwd).  d_o shares o's strides.
+ * MMAE_EINVAL: null / unaligned pointer, head_dim other than 32 / 64, a stride that is not a multiple of 8, or a geometry that would
+ * overflow the kernels' 32-bit indexing (B * H * ceil(N / 128) >= 2^31 workgroups, or a row stride above 2^22 elements). */
+int mmae_attn_fwd_tiled(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int hd,
+                        int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
+                        float scale, void* stream);
+int mmae_attn_bwd_tiled(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, void* dq,
+                        void* dk, void* dv, int B, int H, int Nq, int Nk, int hd, int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr,
+                        int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr, int64_t dq_sb, int64_t dq_sr, int64_t dk_sb, int64_t dk_sr,
+                        int64_t dv_sb, int64_t dv_sr, float scale, void* stream);
 
 
 /* ------------------------------------------------------------------------- *
@@ -416,7 +436,9 @@ int mmae_attn_bwd_f16(const void* q, const void* k, const void* v, const void* o
  * Every buffer is the caller's: activations (forward writes, backward reads), backward temporaries, gradient
  * destinations, and two f32 workspaces (split-K slabs / reduction scratch) private to the two streams.
  * act_dtype MMAE_BF16, or MMAE_F32 with f32_gemm = MMAE_F32X3 (fp32 adapters in speed mode).  Needs the fused attention
- * kernel's geometry (head_dim 32 / 64, N <= 256); otherwise MMAE_ESUPPORT and the caller issues the steps itself.
+ * kernels' geometry: head_dim 32 / 64; N <= 256, or any N with bf16 activations and no MX weights (mmae_attn_fwd_tiled / _bwd_tiled;
+ * the backward then keeps delta, B * heads * N floats, at the start of ws_main between its two attention launches); otherwise
+ * MMAE_ESUPPORT and the caller issues the steps itself.
  * ------------------------------------------------------------------------- */
 typedef struct mmae_block_desc {
     int32_t B, N, D, heads, Hd;                  /* R = B*N rows of width D; Hd = MLP hidden width */

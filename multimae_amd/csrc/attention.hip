@@ -20,6 +20,9 @@
 // and dS right before their MFMA; the backward scales dO by the power of two of the loss gradient's amax (AttnArgs.dy_amax, as
 // the GEMMs' mmae_gemm_desc.a_amax) and unscales dQ / dK / dV at their store.
 //
+// Sequences beyond 256 tokens (bf16): the tiled kernels further down (attn_fwd_tiled_kernel, attn_bwd_tiled_dq_kernel, attn_bwd_tiled_dkdv_kernel) stream
+// K / V (or Q / dO) through LDS in 128-row tiles instead of holding them.
+//
 // Replaces Attention.forward / CrossAttention.forward cores (multimae_utils.py:175-179, 206-210) + autograd.
 #include "common.h"
 #include <mutex>
@@ -58,10 +61,10 @@ template <> __device__ __forceinline__ int tile_off<32>(int row, int c) {
 // rows [0, nrows) of a [.., HD] slice (row stride `sr` elements) -> LDS tile of nrows_pad rows (zero padded).
 // Two-phase so that a kernel can put ALL its tile loads in flight before the first LDS write: with load -> ds_write per
 // chunk (and one loop per tile) every chunk exposed a full HBM round trip -- 8 in a row in the backward prologue.
-template <int HD, int NTHR>
+template <int HD, int NTHR, int MAXR = 256>
 struct TileLoader {
     static constexpr int CPR = HD / 8;
-    static constexpr int MAXIT = (256 * CPR + NTHR - 1) / NTHR;       // nrows_pad <= 256
+    static constexpr int MAXIT = (MAXR * CPR + NTHR - 1) / NTHR;      // nrows_pad <= MAXR
     i32x4 r[MAXIT];
     __device__ __forceinline__ void issue(const uint16_t* base, long long sr, int nrows, int nrows_pad, int tid) {
         const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x80000000, 0x00020000);
@@ -858,6 +861,361 @@ __global__ void __launch_bounds__(256, 2) xattn_fwd_fused_kernel(const XAttnArgs
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// Tiled ("flash-style") bf16 attention for sequences beyond the 256 tokens the LDS-resident kernels above hold: the same S^T = K Q^T layout
+// (a lane owns one query row), the same swizzled tiles, fragments and stores, but K and V (forward, dQ) or Q and dO (dK / dV) stream through
+// LDS in 128-row tiles, double buffered: the loads of tile i + 1 are issued before the products of tile i and committed after them, one barrier
+// per tile.  One workgroup = 4 waves x 32 rows = 128 queries (or keys) of one (batch, head); 4 tiles x 128 x head_dim x 2 B = 64 KB of LDS at
+// head_dim 64, two workgroups per CU.
+//   forward : online softmax -- running max, sum and O accumulator per lane, rescaled once per 128-key tile; writes O (bf16) and the row LSE.
+//   backward: two kernels, no sum across workgroups, no atomics (gradients stay bit-reproducible).
+//     dq    : lane = query.  Sweep 1 over the key tiles forms delta_i = sum_j P_ij dP_ij from its own fp32 P and dP (NOT rowsum(dO . O) with the
+//             stored bf16 O: see the comment in attn_bwd_kernel) and writes it to the f32 scratch; sweep 2 forms dS and accumulates dQ in registers.
+//     dkdv  : lane = key.  Sweeps the query tiles (Q, dO, lse, delta) and accumulates dK and dV in registers.
+//   Nine small products per tile pair against the minimum of five: the price of having neither a hand-off between workgroups nor float atomics.
+// Rows beyond Nq / Nk are zero-filled by the out-of-range buffer offset, never read; every buffer resource is re-based per tile / query block, so
+// that the 32-bit offsets only span 128 rows.
+struct TiledArgs {
+    const uint16_t *q, *k, *v, *d_o;
+    uint16_t *out, *dq, *dk, *dv;
+    float *lse, *delta;
+    int B, H, Nq, Nk;
+    long long q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr, dq_sb, dq_sr, dk_sb, dk_sr, dv_sb, dv_sr;
+    float scale;
+};
+constexpr int TROWS = 128;                                  // rows per LDS tile and per workgroup
+
+template <int HD>
+__global__ void __launch_bounds__(256, 2) attn_fwd_tiled_kernel(const TiledArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int tile_b = TROWS * HD * 2;                  // smem: [K0 | V0 | K1 | V1]
+    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nqb = (a.Nq + TROWS - 1) / TROWS;
+    const int bh = blockIdx.x / nqb, qb = blockIdx.x % nqb;
+    const int b = bh / a.H, h = bh % a.H;
+    const uint16_t* kg = a.k + b * a.k_sb + h * HD;
+    const uint16_t* vg = a.v + b * a.v_sb + h * HD;
+    const int nkt = (a.Nk + TROWS - 1) / TROWS;
+    TileLoader<HD, 256, TROWS> lk, lv;
+    lk.issue(kg, a.k_sr, min(a.Nk, TROWS), TROWS, tid);
+    lv.issue(vg, a.v_sr, min(a.Nk, TROWS), TROWS, tid);
+    const int q0 = qb * TROWS + wave * 32, q = q0 + (lane & 31);
+    const bool qok = q < a.Nq, wact = q0 < a.Nq;            // wact: wave-uniform; an idle wave still loads tiles and meets the barriers
+    bf16x8 qf[HD / 16];
+    {
+        const auto rsQ = __builtin_amdgcn_make_buffer_rsrc((void*)(a.q + b * a.q_sb + h * HD + (long long)q0 * a.q_sr), 0, 0x80000000, 0x00020000);
+#pragma unroll
+        for (int ks = 0; ks < HD / 16; ++ks) qf[ks] = load_frag_global(rsQ, qok, lane & 31, a.q_sr, ks, hi);
+    }
+    lk.commit(smem, TROWS, tid);
+    lv.commit(smem + tile_b, TROWS, tid);
+    __syncthreads();
+    const float sc2 = a.scale * 1.44269504089f;
+    float m = -INFINITY, l = 0.f;
+    f32x16 o[HD / 32];
+#pragma unroll
+    for (int dt = 0; dt < HD / 32; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    for (int kt = 0; kt < nkt; ++kt) {
+        const char* Ks = smem + (kt & 1) * 2 * tile_b;
+        const char* Vs = Ks + tile_b;
+        const bool more = kt + 1 < nkt;
+        if (more) {
+            const int k1 = (kt + 1) * TROWS;
+            lk.issue(kg + (long long)k1 * a.k_sr, a.k_sr, min(a.Nk - k1, TROWS), TROWS, tid);
+            lv.issue(vg + (long long)k1 * a.v_sr, a.v_sr, min(a.Nk - k1, TROWS), TROWS, tid);
+        }
+        if (wact) {
+            const int k0 = kt * TROWS;
+            const int nt = min(4, (a.Nk - k0 + 31) >> 5);  // 32-key sub-tiles of this tile that hold a real key (>= 1)
+            f32x16 s[4];
+            float mg = -INFINITY;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (t < nt) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[t][r] = 0.f;
+#pragma unroll
+                    for (int ks = 0; ks < HD / 16; ++ks) s[t] = mma<0>(frag_rows<HD>(Ks, t * 32, ks, lane), qf[ks], qf[ks], qf[ks], s[t]);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int key = k0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                        const float v = key < a.Nk ? s[t][r] * sc2 : -INFINITY;
+                        s[t][r] = v;
+                        mg = fmaxf(mg, v);
+                    }
+                }
+            }
+            mg = fmaxf(mg, __shfl_xor(mg, 32, 64));
+            const float mn = fmaxf(m, mg);                  // every tile holds at least one real key: mn is finite
+            float lg = 0.f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (t < nt) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) { const float p = __builtin_amdgcn_exp2f(s[t][r] - mn); s[t][r] = p; lg += p; }
+                }
+            }
+            lg += __shfl_xor(lg, 32, 64);
+            const float alpha = __builtin_amdgcn_exp2f(m - mn);      // first tile: m = -inf -> alpha = 0 on zeros
+            l = l * alpha + lg;
+#pragma unroll
+            for (int dt = 0; dt < HD / 32; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+            m = mn;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (t < nt) {
+#pragma unroll
+                    for (int sI = 0; sI < 2; ++sI) {
+                        const bf16x8 pf = pack8(s[t], sI);
+#pragma unroll
+                        for (int dt = 0; dt < HD / 32; ++dt) o[dt] = mma<0>(frag_cols<HD>(Vs, dt * 32, t * 32 + 16 * sI, lane), pf, pf, pf, o[dt]);
+                    }
+                }
+            }
+        }
+        if (more) {
+            char* nx = smem + ((kt + 1) & 1) * 2 * tile_b;
+            lk.commit(nx, TROWS, tid);
+            lv.commit(nx + tile_b, TROWS, tid);
+        }
+        __syncthreads();
+    }
+    if (wact) {
+        const float inv = 1.0f / l;
+        uint16_t* ob = a.out + b * a.o_sb + h * HD + (long long)q * a.o_sr;
+#pragma unroll
+        for (int dt = 0; dt < HD / 32; ++dt) store_row32<false>(ob + dt * 32, o[dt], inv, hi, qok);
+        if (qok && hi == 0) a.lse[((long long)b * a.H + h) * a.Nq + q] = m * 0.69314718056f + __logf(l);
+    }
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256, 2) attn_bwd_tiled_dq_kernel(const TiledArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int tile_b = TROWS * HD * 2;                  // smem: [K0 | V0 | K1 | V1]
+    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nqb = (a.Nq + TROWS - 1) / TROWS;
+    const int bh = blockIdx.x / nqb, qb = blockIdx.x % nqb;
+    const int b = bh / a.H, h = bh % a.H;
+    const uint16_t* kg = a.k + b * a.k_sb + h * HD;
+    const uint16_t* vg = a.v + b * a.v_sb + h * HD;
+    const int nkt = (a.Nk + TROWS - 1) / TROWS;
+    TileLoader<HD, 256, TROWS> lk, lv;
+    lk.issue(kg, a.k_sr, min(a.Nk, TROWS), TROWS, tid);
+    lv.issue(vg, a.v_sr, min(a.Nk, TROWS), TROWS, tid);
+    const int q0 = qb * TROWS + wave * 32, q = q0 + (lane & 31);
+    const bool qok = q < a.Nq, wact = q0 < a.Nq;
+    bf16x8 qf[HD / 16], dof[HD / 16];
+    {
+        const auto rsQ = __builtin_amdgcn_make_buffer_rsrc((void*)(a.q + b * a.q_sb + h * HD + (long long)q0 * a.q_sr), 0, 0x80000000, 0x00020000);
+        const auto rsO = __builtin_amdgcn_make_buffer_rsrc((void*)(a.d_o + b * a.o_sb + h * HD + (long long)q0 * a.o_sr), 0, 0x80000000, 0x00020000);
+#pragma unroll
+        for (int ks = 0; ks < HD / 16; ++ks) {
+            qf[ks] = load_frag_global(rsQ, qok, lane & 31, a.q_sr, ks, hi);
+            dof[ks] = load_frag_global(rsO, qok, lane & 31, a.o_sr, ks, hi);
+        }
+    }
+    const long long li = ((long long)b * a.H + h) * a.Nq + q;
+    const float lse_q = qok ? a.lse[li] * 1.44269504089f : 0.f;      // base-2 domain, as attn_bwd_kernel
+    lk.commit(smem, TROWS, tid);
+    lv.commit(smem + tile_b, TROWS, tid);
+    __syncthreads();
+    const float sc2 = a.scale * 1.44269504089f;
+    float d0 = 0.f, d1 = 0.f, delta_q = 0.f;
+    f32x16 dq[HD / 32];
+#pragma unroll
+    for (int dt = 0; dt < HD / 32; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+    // sweep 1 (it < nkt): delta; sweep 2: dS and dQ.  One loop, so that the double buffering runs on across the seam.
+    for (int it = 0; it < 2 * nkt; ++it) {
+        const char* Ks = smem + (it & 1) * 2 * tile_b;
+        const char* Vs = Ks + tile_b;
+        const bool more = it + 1 < 2 * nkt;
+        const int kt = it < nkt ? it : it - nkt;
+        if (more) {
+            const int k1 = (it + 1 < nkt ? it + 1 : it + 1 - nkt) * TROWS;
+            lk.issue(kg + (long long)k1 * a.k_sr, a.k_sr, min(a.Nk - k1, TROWS), TROWS, tid);
+            lv.issue(vg + (long long)k1 * a.v_sr, a.v_sr, min(a.Nk - k1, TROWS), TROWS, tid);
+        }
+        if (wact) {
+            const int nt = min(4, (a.Nk - kt * TROWS + 31) >> 5);
+            for (int t = 0; t < nt; ++t) {
+                f32x16 st, dpt;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { st[r] = 0.f; dpt[r] = 0.f; }
+#pragma unroll
+                for (int ks = 0; ks < HD / 16; ++ks) {
+                    st = mma<0>(frag_rows<HD>(Ks, t * 32, ks, lane), qf[ks], qf[ks], qf[ks], st);
+                    dpt = mma<0>(frag_rows<HD>(Vs, t * 32, ks, lane), dof[ks], dof[ks], dof[ks], dpt);
+                }
+                // (zero-filled keys: dP is exactly 0 there and their K rows are 0, whatever exp(-lse) their P is)
+                if (it < nkt) {
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        d0 += __builtin_amdgcn_exp2f(st[r] * sc2 - lse_q) * dpt[r];
+                        d1 += __builtin_amdgcn_exp2f(st[r + 1] * sc2 - lse_q) * dpt[r + 1];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float p = __builtin_amdgcn_exp2f(st[r] * sc2 - lse_q);
+                        st[r] = p * (dpt[r] * a.scale - delta_q);    // dS^T
+                    }
+#pragma unroll
+                    for (int sI = 0; sI < 2; ++sI) {
+                        const bf16x8 dsf = pack8(st, sI);
+#pragma unroll
+                        for (int dt = 0; dt < HD / 32; ++dt) dq[dt] = mma<0>(frag_cols<HD>(Ks, dt * 32, t * 32 + 16 * sI, lane), dsf, dsf, dsf, dq[dt]);
+                    }
+                }
+            }
+            if (it == nkt - 1) {
+                float d = d0 + d1;
+                d += __shfl_xor(d, 32, 64);
+                if (qok && hi == 0) a.delta[li] = d;        // for the dK / dV kernel
+                delta_q = d * a.scale;
+            }
+        }
+        if (more) {
+            char* nx = smem + ((it + 1) & 1) * 2 * tile_b;
+            lk.commit(nx, TROWS, tid);
+            lv.commit(nx + tile_b, TROWS, tid);
+        }
+        __syncthreads();
+    }
+    if (wact) {
+        uint16_t* dst = a.dq + b * a.dq_sb + h * HD + (long long)q * a.dq_sr;
+#pragma unroll
+        for (int dt = 0; dt < HD / 32; ++dt) store_row32<false>(dst + dt * 32, dq[dt], 1.0f, hi, qok);
+    }
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256, 2) attn_bwd_tiled_dkdv_kernel(const TiledArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int tile_b = TROWS * HD * 2;                  // smem: [Q0 | dO0 | Q1 | dO1 | lse0 delta0 | lse1 delta1]
+    float* rowc = (float*)(smem + 4 * tile_b);
+    const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nkb = (a.Nk + TROWS - 1) / TROWS;
+    const int bh = blockIdx.x / nkb, kb = blockIdx.x % nkb;
+    const int b = bh / a.H, h = bh % a.H;
+    const uint16_t* qg = a.q + b * a.q_sb + h * HD;
+    const uint16_t* dog = a.d_o + b * a.o_sb + h * HD;
+    const float* rc_src = (tid < TROWS ? a.lse : a.delta) + ((long long)b * a.H + h) * a.Nq;
+    const float rc_mul = tid < TROWS ? 1.44269504089f : a.scale;     // lse in the base-2 domain; delta times the score scale
+    const int nqt = (a.Nq + TROWS - 1) / TROWS;
+    TileLoader<HD, 256, TROWS> lq, ld;
+    lq.issue(qg, a.q_sr, min(a.Nq, TROWS), TROWS, tid);
+    ld.issue(dog, a.o_sr, min(a.Nq, TROWS), TROWS, tid);
+    float rc = (tid & (TROWS - 1)) < a.Nq ? rc_src[tid & (TROWS - 1)] * rc_mul : 0.f;
+    const int key0 = kb * TROWS + wave * 32, key = key0 + (lane & 31);
+    const bool kok = key < a.Nk, wact = key0 < a.Nk;
+    bf16x8 kf[HD / 16], vf[HD / 16];
+    {
+        const auto rsK = __builtin_amdgcn_make_buffer_rsrc((void*)(a.k + b * a.k_sb + h * HD + (long long)key0 * a.k_sr), 0, 0x80000000, 0x00020000);
+        const auto rsV = __builtin_amdgcn_make_buffer_rsrc((void*)(a.v + b * a.v_sb + h * HD + (long long)key0 * a.v_sr), 0, 0x80000000, 0x00020000);
+#pragma unroll
+        for (int ks = 0; ks < HD / 16; ++ks) {
+            kf[ks] = load_frag_global(rsK, kok, lane & 31, a.k_sr, ks, hi);
+            vf[ks] = load_frag_global(rsV, kok, lane & 31, a.v_sr, ks, hi);
+        }
+    }
+    lq.commit(smem, TROWS, tid);
+    ld.commit(smem + tile_b, TROWS, tid);
+    rowc[tid] = rc;
+    __syncthreads();
+    const float sc2 = a.scale * 1.44269504089f;
+    f32x16 dk[HD / 32], dv[HD / 32];
+#pragma unroll
+    for (int dt = 0; dt < HD / 32; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
+    for (int qt = 0; qt < nqt; ++qt) {
+        const char* Qs = smem + (qt & 1) * 2 * tile_b;
+        const char* dOs = Qs + tile_b;
+        const float* lse_s = rowc + (qt & 1) * 2 * TROWS;
+        const float* delta_s = lse_s + TROWS;
+        const bool more = qt + 1 < nqt;
+        if (more) {
+            const int q1 = (qt + 1) * TROWS;
+            lq.issue(qg + (long long)q1 * a.q_sr, a.q_sr, min(a.Nq - q1, TROWS), TROWS, tid);
+            ld.issue(dog + (long long)q1 * a.o_sr, a.o_sr, min(a.Nq - q1, TROWS), TROWS, tid);
+            const int qi = q1 + (tid & (TROWS - 1));
+            rc = qi < a.Nq ? rc_src[qi] * rc_mul : 0.f;
+        }
+        if (wact) {
+            const int nqs = min(4, (a.Nq - qt * TROWS + 31) >> 5);
+            for (int qs = 0; qs < nqs; ++qs) {
+                f32x16 sm, dp;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { sm[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+                for (int ks = 0; ks < HD / 16; ++ks) {
+                    sm = mma<0>(frag_rows<HD>(Qs, qs * 32, ks, lane), kf[ks], kf[ks], kf[ks], sm);
+                    dp = mma<0>(frag_rows<HD>(dOs, qs * 32, ks, lane), vf[ks], vf[ks], vf[ks], dp);
+                }
+                // (zero-filled queries: lse = delta = 0 and dO = Q = 0, so P = 1 meets dO = 0 and dS = 0)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int qr = qs * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    const float p = __builtin_amdgcn_exp2f(sm[r] * sc2 - lse_s[qr]);
+                    sm[r] = p;                                        // P
+                    dp[r] = p * (dp[r] * a.scale - delta_s[qr]);      // dS
+                }
+#pragma unroll
+                for (int sI = 0; sI < 2; ++sI) {
+                    const bf16x8 pf = pack8(sm, sI), dsf = pack8(dp, sI);
+#pragma unroll
+                    for (int dt = 0; dt < HD / 32; ++dt) {
+                        dv[dt] = mma<0>(frag_cols<HD>(dOs, dt * 32, qs * 32 + 16 * sI, lane), pf, pf, pf, dv[dt]);
+                        dk[dt] = mma<0>(frag_cols<HD>(Qs, dt * 32, qs * 32 + 16 * sI, lane), dsf, dsf, dsf, dk[dt]);
+                    }
+                }
+            }
+        }
+        if (more) {
+            char* nx = smem + ((qt + 1) & 1) * 2 * tile_b;
+            lq.commit(nx, TROWS, tid);
+            ld.commit(nx + tile_b, TROWS, tid);
+            rowc[((qt + 1) & 1) * 2 * TROWS + tid] = rc;
+        }
+        __syncthreads();
+    }
+    if (wact) {
+        uint16_t* dkd = a.dk + b * a.dk_sb + h * HD + (long long)key * a.dk_sr;
+        uint16_t* dvd = a.dv + b * a.dv_sb + h * HD + (long long)key * a.dv_sr;
+#pragma unroll
+        for (int dt = 0; dt < HD / 32; ++dt) {
+            store_row32<false>(dkd + dt * 32, dk[dt], 1.0f, hi, kok);
+            store_row32<false>(dvd + dt * 32, dv[dt], 1.0f, hi, kok);
+        }
+    }
+}
+
+// geometry the tiled kernels index with 32 bits: the workgroup count, and the byte offsets inside one 128-row tile
+int check_tiled(int B, int H, int Nq, int Nk, int hd, const long long* strides, int n) {
+    if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return -1;
+    if (hd != 32 && hd != 64) return -2;
+    for (int i = 0; i < n; ++i) if (strides[i] % 8) return -3;
+    const long long nb = (long long)B * H * ((std::max(Nq, Nk) + TROWS - 1) / TROWS);
+    if (nb >= (1ll << 31)) return -4;
+    for (int i = 1; i < n; i += 2) if (strides[i] < 0 || strides[i] > (1ll << 22)) return -4;      // row strides: 128 rows x 2 B stay below 2^31
+    return 0;
+}
+const char* tiled_msg(int rc) {
+    return rc == -2 ? "attn_tiled: head_dim must be 32 or 64" : rc == -3 ? "attn_tiled: strides must be multiples of 8"
+         : rc == -4 ? "attn_tiled: geometry would overflow the kernels' 32-bit indexing (B * H * ceil(N / 128) < 2^31 workgroups, 0 <= row stride <= 2^22 elements)"
+                    : "attn_tiled: need B, H, Nq, Nk >= 1";
+}
+
 int check_common(int B, int H, int Nq, int Nk, int hd, const long long* strides, int n) {
     if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || Nq > 256 || Nk > 256) return -1;
     if (hd != 32 && hd != 64) return -2;
@@ -1054,6 +1412,69 @@ int mmae_attn_bwd_f16(const void* q, const void* k, const void* v, const void* o
                       int64_t dv_sr, float scale, void* stream) {
     return attn_bwd_impl(3, q, k, v, o, d_o, lse, dq, dk, dv, B, H, Nq, Nk, hd, q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr, dq_sb,
                          dq_sr, dk_sb, dk_sr, dv_sb, dv_sr, scale, stream);
+}
+
+/* Tiled bf16 attention, any sequence length (see the kernels' header comment).  Same operands and lse as mmae_attn_fwd. */
+int mmae_attn_fwd_tiled(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int hd,
+                        int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
+                        float scale, void* stream) {
+    MMAE_REQUIRE(q && k && v && o && lse, "attn_fwd_tiled: null pointer");
+    const long long st[] = {q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr};
+    const int rc = check_tiled(B, H, Nq, Nk, hd, st, 8);
+    MMAE_REQUIRE(rc == 0, tiled_msg(rc));
+    MMAE_REQUIRE(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)o % 16 == 0), "attn_fwd_tiled: unaligned pointer");
+    TiledArgs a = {};
+    a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.out = (uint16_t*)o; a.lse = lse;
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk;
+    a.q_sb = q_sb; a.q_sr = q_sr; a.k_sb = k_sb; a.k_sr = k_sr; a.v_sb = v_sb; a.v_sr = v_sr; a.o_sb = o_sb; a.o_sr = o_sr;
+    a.scale = scale;
+    const size_t lds = (size_t)4 * TROWS * hd * 2;
+    const dim3 grid((unsigned)(B * H * ((Nq + TROWS - 1) / TROWS)));
+    static std::once_flag once;
+    std::call_once(once, [] {
+        (void)hipFuncSetAttribute((const void*)attn_fwd_tiled_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 64 * 2);
+        (void)hipFuncSetAttribute((const void*)attn_fwd_tiled_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 32 * 2);
+    });
+    if (hd == 64) hipLaunchKernelGGL(attn_fwd_tiled_kernel<64>, grid, dim3(256), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(attn_fwd_tiled_kernel<32>, grid, dim3(256), lds, (hipStream_t)stream, a);
+    return mmae_check_launch("attn_fwd_tiled");
+}
+
+/* Backward of mmae_attn_fwd_tiled: two launches (dq, which also writes delta; then dk / dv, which reads it).  o is accepted for symmetry with
+ * mmae_attn_bwd and not read: delta comes from the kernels' own fp32 P and dP. */
+int mmae_attn_bwd_tiled(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, void* dq,
+                        void* dk, void* dv, int B, int H, int Nq, int Nk, int hd, int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr,
+                        int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr, int64_t dq_sb, int64_t dq_sr, int64_t dk_sb, int64_t dk_sr,
+                        int64_t dv_sb, int64_t dv_sr, float scale, void* stream) {
+    MMAE_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv, "attn_bwd_tiled: null pointer");
+    const long long st[] = {q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr, dq_sb, dq_sr, dk_sb, dk_sr, dv_sb, dv_sr};
+    const int rc = check_tiled(B, H, Nq, Nk, hd, st, 14);
+    MMAE_REQUIRE(rc == 0, tiled_msg(rc));
+    MMAE_REQUIRE(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)d_o % 16 == 0), "attn_bwd_tiled: unaligned pointer");
+    MMAE_REQUIRE(((uintptr_t)dq % 16 == 0) && ((uintptr_t)dk % 16 == 0) && ((uintptr_t)dv % 16 == 0), "attn_bwd_tiled: unaligned output pointer");
+    TiledArgs a = {};
+    a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.d_o = (const uint16_t*)d_o;
+    a.dq = (uint16_t*)dq; a.dk = (uint16_t*)dk; a.dv = (uint16_t*)dv; a.lse = (float*)lse; a.delta = delta;
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk;
+    a.q_sb = q_sb; a.q_sr = q_sr; a.k_sb = k_sb; a.k_sr = k_sr; a.v_sb = v_sb; a.v_sr = v_sr; a.o_sb = o_sb; a.o_sr = o_sr;
+    a.dq_sb = dq_sb; a.dq_sr = dq_sr; a.dk_sb = dk_sb; a.dk_sr = dk_sr; a.dv_sb = dv_sb; a.dv_sr = dv_sr;
+    a.scale = scale;
+    const size_t lds_q = (size_t)4 * TROWS * hd * 2, lds_k = lds_q + (size_t)4 * TROWS * 4;
+    const dim3 grid_q((unsigned)(B * H * ((Nq + TROWS - 1) / TROWS))), grid_k((unsigned)(B * H * ((Nk + TROWS - 1) / TROWS)));
+    static std::once_flag once;
+    std::call_once(once, [] {
+        (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_dq_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 64 * 2);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_dq_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 32 * 2);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_dkdv_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 64 * 2 + 4 * TROWS * 4);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_dkdv_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 32 * 2 + 4 * TROWS * 4);
+    });
+    if (hd == 64) hipLaunchKernelGGL(attn_bwd_tiled_dq_kernel<64>, grid_q, dim3(256), lds_q, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(attn_bwd_tiled_dq_kernel<32>, grid_q, dim3(256), lds_q, (hipStream_t)stream, a);
+    int rl = mmae_check_launch("attn_bwd_tiled (dq)");
+    if (rl) return rl;
+    if (hd == 64) hipLaunchKernelGGL(attn_bwd_tiled_dkdv_kernel<64>, grid_k, dim3(256), lds_k, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(attn_bwd_tiled_dkdv_kernel<32>, grid_k, dim3(256), lds_k, (hipStream_t)stream, a);
+    return mmae_check_launch("attn_bwd_tiled (dk, dv)");
 }
 
 }  // extern "C"

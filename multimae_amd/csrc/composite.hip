@@ -368,7 +368,9 @@ int check_desc(const mmae_block_desc* d) {
         mmae_set_error("block: fp16 storage needs D, Hd multiples of 32, no stochastic depth, no MX weights"); return MMAE_ESUPPORT;
     }
     const int hd = d->D / d->heads;
-    if ((hd != 32 && hd != 64) || d->N > 256) { mmae_set_error("block: geometry outside the fused attention kernel (head_dim 32/64, N <= 256)"); return MMAE_ESUPPORT; }
+    // beyond 256 tokens: the tiled attention kernels (bf16 activations, bf16 products); every other dtype keeps the LDS-resident kernel's limit
+    const bool tiled_ok = d->act_dtype == MMAE_BF16 && !d->mx_w;
+    if ((hd != 32 && hd != 64) || (d->N > 256 && !tiled_ok)) { mmae_set_error("block: geometry outside the fused attention kernel (head_dim 32/64, N <= 256)"); return MMAE_ESUPPORT; }
     MMAE_REQUIRE(d->qkv_w && d->proj_w && d->fc1_w && d->fc2_w && d->n1_w && d->n1_b && d->qkv_b && d->proj_b && d->n2_w && d->n2_b &&
                  d->fc1_b && d->fc2_b, "block: null parameter");
     MMAE_REQUIRE(d->x0 && d->ln1 && d->mean1 && d->rstd1 && d->qkv && d->lse && d->ao && d->x1 && d->ln2 && d->mean2 && d->rstd2 &&
@@ -392,7 +394,8 @@ int attn_strides_fwd(const mmae_block_desc* d, hipStream_t st, void* mx_q = null
     if (mx_q)
         return mmae_attn_fwd_mx(qkv, qkv + (size_t)D * es, qkv + (size_t)2 * D * es, d->ao, d->lse, d->B, d->heads, N, N, hd, (int64_t)N * 3 * D, 3 * D,
                                 (int64_t)N * 3 * D, 3 * D, (int64_t)N * 3 * D, 3 * D, (int64_t)N * D, D, scale, mx_q, mx_s, st);
-    auto fn = d->act_dtype == MMAE_BF16 ? mmae_attn_fwd : (d->act_dtype == MMAE_F16 ? mmae_attn_fwd_f16 : (d->f32_gemm == MMAE_F32F16 ? mmae_attn_fwd_f32f16 : mmae_attn_fwd_f32x3));
+    auto fn = d->act_dtype == MMAE_BF16 ? (N > 256 ? mmae_attn_fwd_tiled : mmae_attn_fwd)
+                                        : (d->act_dtype == MMAE_F16 ? mmae_attn_fwd_f16 : (d->f32_gemm == MMAE_F32F16 ? mmae_attn_fwd_f32f16 : mmae_attn_fwd_f32x3));
     return fn(qkv, qkv + (size_t)D * es, qkv + (size_t)2 * D * es, d->ao, d->lse, d->B, d->heads, N, N, hd, (int64_t)N * 3 * D, 3 * D,
               (int64_t)N * 3 * D, 3 * D, (int64_t)N * 3 * D, 3 * D, (int64_t)N * D, D, scale, st);
 }
@@ -460,7 +463,8 @@ int check_stack(const mmae_stack_desc* d) {
     MMAE_REQUIRE(d->act_dtype == MMAE_BF16 || (d->act_dtype == MMAE_F32 && (d->f32_gemm == MMAE_F32X3 || d->f32_gemm == MMAE_F32F16)),
                  "stack: activations must be bf16, or f32 with split-bf16 (MMAE_F32X3) / fp16-operand (MMAE_F32F16) products");
     const int hd = d->D / d->heads;
-    if ((hd != 32 && hd != 64) || d->N > 256) { mmae_set_error("stack: geometry outside the fused attention kernel (head_dim 32/64, N <= 256)"); return MMAE_ESUPPORT; }
+    const bool tiled_ok = d->act_dtype == MMAE_BF16 && !d->mx_w;      // as check_desc
+    if ((hd != 32 && hd != 64) || (d->N > 256 && !tiled_ok)) { mmae_set_error("stack: geometry outside the fused attention kernel (head_dim 32/64, N <= 256)"); return MMAE_ESUPPORT; }
     MMAE_REQUIRE(d->w && d->p && d->x && d->act, "stack: null pointer");
     if (d->mx_w) {
         MMAE_REQUIRE(d->act_dtype == MMAE_BF16, "stack: MX-fp8 products need bf16 activations");
@@ -728,6 +732,12 @@ int mmae_block_bwd(const mmae_block_desc* d, void* stream, void* side_stream) {
             if ((rc = mmae_attn_bwd_f32f16(qkv, qkv + (size_t)D * es, qkv + (size_t)2 * D * es, d->ao, d->d_ao, d->lse, dq, dq + (size_t)D * es,
                                            dq + (size_t)2 * D * es, d->B, d->heads, N, N, hd, sb3, 3 * D, sb3, 3 * D, sb3, 3 * D, sb1, D, sb3, 3 * D,
                                            sb3, 3 * D, sb3, 3 * D, 1.0f / sqrtf((float)hd), c.dy_amax, st))) return rc;
+        } else if (N > 256) {                             // tiled kernels (check_desc: bf16, no MX); delta lives in the main stream's workspace between its two launches
+            const int64_t nd = (int64_t)d->B * d->heads * N;
+            MMAE_REQUIRE(d->ws_main && d->ws_main_elems >= nd, "block_bwd: ws_main too small for the attention delta (B * heads * N f32)");
+            if ((rc = mmae_attn_bwd_tiled(qkv, qkv + (size_t)D * es, qkv + (size_t)2 * D * es, d->ao, d->d_ao, d->lse, d->ws_main, dq, dq + (size_t)D * es,
+                                          dq + (size_t)2 * D * es, d->B, d->heads, N, N, hd, sb3, 3 * D, sb3, 3 * D, sb3, 3 * D, sb1, D, sb3, 3 * D, sb3, 3 * D,
+                                          sb3, 3 * D, 1.0f / sqrtf((float)hd), st))) return rc;
         } else
         if (hq >= 0) {                                    // MX mode: the kernel leaves the quantised d_qkv in half 0 for the qkv dX product
             void *gq, *gs;

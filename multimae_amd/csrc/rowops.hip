@@ -304,7 +304,7 @@ __global__ void __launch_bounds__(256) colsum_scalar_kernel(const DT* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// Row softmax over materialised scores, n <= 256.  One wave per row; lane l owns l, l+64, ...
+// Row softmax over materialised scores, ld <= 256.  One wave per row; lane l owns l, l+64, ...  (longer rows: the _long kernels below)
 // ------------------------------------------------------------------------------------------
 template <typename PT>
 __global__ void __launch_bounds__(256) softmax_fwd_kernel(const float* __restrict__ S, long long lds_, PT* __restrict__ P,
@@ -357,6 +357,42 @@ __global__ void __launch_bounds__(256) softmax_bwd_kernel(const PT* __restrict__
         const int c = lane + 64 * i;
         if (c < ldds) ActT<PT>::st(dS + row * ldds + c, (c < n) ? scale * p[i] * (d[i] - dot) : 0.f);
     }
+}
+
+// Rows longer than 256: the same wave-per-row scheme, but the row is walked in passes (max, sum, store / dot, store) instead of being held in
+// registers.  This is the materialised-score reference path at fine-tuning sequence lengths (the A/B partner of the tiled attention kernels and
+// the route of the f32 parity mode), not a hot path.
+template <typename PT>
+__global__ void __launch_bounds__(256) softmax_fwd_long_kernel(const float* __restrict__ S, long long lds_, PT* __restrict__ P,
+                                                               long long ldp, long long rows, int n, float scale) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* s = S + row * lds_;
+    float mx = -INFINITY;
+    for (int c = lane; c < n; c += 64) mx = fmaxf(mx, s[c] * scale);
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int c = lane; c < n; c += 64) sum += expf(s[c] * scale - mx);
+    sum = wave_sum(sum);
+    const float inv = 1.0f / sum;
+    PT* p = P + row * ldp;
+    for (long long c = lane; c < ldp; c += 64) ActT<PT>::st(p + c, (c < n) ? expf(s[c] * scale - mx) * inv : 0.f);
+}
+
+template <typename PT>
+__global__ void __launch_bounds__(256) softmax_bwd_long_kernel(const PT* __restrict__ P, long long ldp,
+                                                               const float* __restrict__ dP, long long lddp,
+                                                               PT* __restrict__ dS, long long ldds, long long rows, int n,
+                                                               float scale) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float dot = 0.f;
+    for (int c = lane; c < n; c += 64) dot += ActT<PT>::ld(P + row * ldp + c) * dP[row * lddp + c];
+    dot = wave_sum(dot);
+    for (long long c = lane; c < ldds; c += 64)
+        ActT<PT>::st(dS + row * ldds + c, (c < n) ? scale * ActT<PT>::ld(P + row * ldp + c) * (dP[row * lddp + c] - dot) : 0.f);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -849,9 +885,14 @@ int mmae_colsum_batch(const mmae_colsum_job* jobs, int n, int accumulate, float*
 int mmae_softmax_fwd(const float* S, int64_t lds_, void* P, int p_dtype, int64_t ldp, int64_t rows, int n, float scale,
                      void* stream) {
     MMAE_REQUIRE(S && P && rows > 0, "softmax_fwd: bad argument");
-    MMAE_REQUIRE(n >= 1 && n <= 256 && ldp >= n && ldp <= 256 && lds_ >= n, "softmax_fwd: need 1 <= n <= ld <= 256");
+    MMAE_REQUIRE(n >= 1 && ldp >= n && lds_ >= n, "softmax_fwd: need 1 <= n <= ld");
     dim3 grid((unsigned)cdiv64(rows, 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
+    if (ldp > 256) {                                      // long rows: the multi-pass kernel
+        if (p_dtype == MMAE_BF16) hipLaunchKernelGGL((softmax_fwd_long_kernel<uint16_t>), grid, block, 0, st, S, (long long)lds_, (uint16_t*)P, (long long)ldp, (long long)rows, n, scale);
+        else hipLaunchKernelGGL((softmax_fwd_long_kernel<float>), grid, block, 0, st, S, (long long)lds_, (float*)P, (long long)ldp, (long long)rows, n, scale);
+        return mmae_check_launch("softmax_fwd");
+    }
     if (p_dtype == MMAE_BF16) hipLaunchKernelGGL((softmax_fwd_kernel<uint16_t>), grid, block, 0, st, S, (long long)lds_, (uint16_t*)P, (long long)ldp, (long long)rows, n, scale);
     else hipLaunchKernelGGL((softmax_fwd_kernel<float>), grid, block, 0, st, S, (long long)lds_, (float*)P, (long long)ldp, (long long)rows, n, scale);
     return mmae_check_launch("softmax_fwd");
@@ -860,9 +901,14 @@ int mmae_softmax_fwd(const float* S, int64_t lds_, void* P, int p_dtype, int64_t
 int mmae_softmax_bwd(const void* P, int p_dtype, int64_t ldp, const float* dP, int64_t lddp, void* dS, int64_t ldds,
                      int64_t rows, int n, float scale, void* stream) {
     MMAE_REQUIRE(P && dP && dS && rows > 0, "softmax_bwd: bad argument");
-    MMAE_REQUIRE(n >= 1 && n <= 256 && ldp >= n && ldds >= n && ldds <= 256 && lddp >= n, "softmax_bwd: need 1 <= n <= ld <= 256");
+    MMAE_REQUIRE(n >= 1 && ldp >= n && ldds >= n && lddp >= n, "softmax_bwd: need 1 <= n <= ld");
     dim3 grid((unsigned)cdiv64(rows, 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
+    if (ldds > 256) {
+        if (p_dtype == MMAE_BF16) hipLaunchKernelGGL((softmax_bwd_long_kernel<uint16_t>), grid, block, 0, st, (const uint16_t*)P, (long long)ldp, dP, (long long)lddp, (uint16_t*)dS, (long long)ldds, (long long)rows, n, scale);
+        else hipLaunchKernelGGL((softmax_bwd_long_kernel<float>), grid, block, 0, st, (const float*)P, (long long)ldp, dP, (long long)lddp, (float*)dS, (long long)ldds, (long long)rows, n, scale);
+        return mmae_check_launch("softmax_bwd");
+    }
     if (p_dtype == MMAE_BF16) hipLaunchKernelGGL((softmax_bwd_kernel<uint16_t>), grid, block, 0, st, (const uint16_t*)P, (long long)ldp, dP, (long long)lddp, (uint16_t*)dS, (long long)ldds, (long long)rows, n, scale);
     else hipLaunchKernelGGL((softmax_bwd_kernel<float>), grid, block, 0, st, (const float*)P, (long long)ldp, dP, (long long)lddp, (float*)dS, (long long)ldds, (long long)rows, n, scale);
     return mmae_check_launch("softmax_bwd");

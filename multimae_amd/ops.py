@@ -379,10 +379,12 @@ def stream_workspace(stream_handle: int, device, elems: Optional[int] = None) ->
 def block_composite_ok(x: Tensor, act: torch.dtype, heads: int, N: int) -> bool:
     D = x.shape[1]
     hd = D // heads
-    if not (_COMPOSITE[0] and _FUSED_ATTN[0] and _device_ok(x) and hd in (32, 64) and N <= 256 and D % 8 == 0):
+    if not (_COMPOSITE[0] and _FUSED_ATTN[0] and _device_ok(x) and hd in (32, 64) and D % 8 == 0):
         return False
-    if act == torch.bfloat16:
+    if act == torch.bfloat16:                             # any N: beyond 256 tokens the composites call the tiled attention kernels
         return True
+    if N > 256:
+        return False
     lds_bwd = 4 * 2 * round_up(N, 32) * hd * 2 + 8 * round_up(N, 32)
     return act == torch.float32 and _f32_split() and lds_bwd <= 160 * 1024
 
@@ -1062,14 +1064,23 @@ def _ptr(v: AttnView) -> int:
 
 
 def _fusable(q: AttnView, k: AttnView, hd: int) -> bool:
-    if not (_FUSED_ATTN[0] and hd in (32, 64) and q.N <= 256 and k.N <= 256):
+    if not (_FUSED_ATTN[0] and hd in (32, 64)):
         return False
-    if q.t.dtype in (torch.bfloat16, torch.float16):
+    if q.t.dtype == torch.bfloat16:                       # any length: the tiled kernels take over beyond 256 tokens
+        return True
+    if q.N > 256 or k.N > 256:
+        return False
+    if q.t.dtype == torch.float16:
         return True
     # f32 activations: only where the surrounding GEMMs are split-bf16 too (fp32 adapters in speed mode); the backward's
     # eight hi/lo tiles must fit the 160 KB LDS
     lds_bwd = 4 * (round_up(q.N, 32) + round_up(k.N, 32)) * hd * 2 + 8 * round_up(q.N, 32)
     return q.t.dtype == torch.float32 and _f32_split() and lds_bwd <= 160 * 1024
+
+
+def _tiled(q: AttnView, k: AttnView) -> bool:
+    """bf16 operands beyond the 256 tokens of the LDS-resident kernel: the tiled kernels (mmae_attn_fwd_tiled / _bwd_tiled)."""
+    return q.t.dtype == torch.bfloat16 and (q.N > 256 or k.N > 256)
 
 
 def attention_fwd(q: AttnView, k: AttnView, v: AttnView, out: AttnView, B: int, H: int, hd: int, scale: float, f16: bool = False,
@@ -1082,6 +1093,11 @@ def attention_fwd(q: AttnView, k: AttnView, v: AttnView, out: AttnView, B: int, 
     dev, act = q.t.device, q.t.dtype
     if drop_p <= 0.0 and _fusable(q, k, hd):
         lse = torch.empty((B, H, Nq), device=dev, dtype=torch.float32)
+        if _tiled(q, k):
+            check(_lib.load().mmae_attn_fwd_tiled(_ptr(q), _ptr(k), _ptr(v), _ptr(out), lse.data_ptr(), B, H, Nq, Nk, hd,
+                                                  Nq * q.ld, q.ld, Nk * k.ld, k.ld, Nk * v.ld, v.ld, Nq * out.ld, out.ld, scale, _stream()),
+                  'attn_fwd_tiled')
+            return ('fused', lse)
         fwd = _lib.load().mmae_attn_fwd if act == torch.bfloat16 else (_lib.load().mmae_attn_fwd_f16 if act == torch.float16 else (
             _lib.load().mmae_attn_fwd_f32f16 if f16 else _lib.load().mmae_attn_fwd_f32x3))
         check(fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), lse.data_ptr(), B, H, Nq, Nk, hd,
@@ -1132,6 +1148,13 @@ def attention_bwd(q: AttnView, k: AttnView, v: AttnView, state, out: AttnView, d
         check(_lib.load().mmae_attn_bwd_f32f16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(d_out), state[1].data_ptr(), _ptr(dq), _ptr(dk), _ptr(dv),
                                                B, H, Nq, Nk, hd, Nq * q.ld, q.ld, Nk * k.ld, k.ld, Nk * v.ld, v.ld, Nq * out.ld, out.ld, Nq * dq.ld,
                                                dq.ld, Nk * dk.ld, dk.ld, Nk * dv.ld, dv.ld, scale, _p(dy_amax), _stream()), 'attn_bwd_f32f16')
+        return
+    if state[0] == 'fused' and _tiled(q, k):
+        assert d_out.ld == out.ld
+        delta = torch.empty((B, H, Nq), device=q.t.device, dtype=torch.float32)      # sum_j P_ij dP_ij: the dq kernel writes it, the dk / dv kernel reads it
+        check(_lib.load().mmae_attn_bwd_tiled(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(d_out), state[1].data_ptr(), delta.data_ptr(), _ptr(dq), _ptr(dk),
+                                              _ptr(dv), B, H, Nq, Nk, hd, Nq * q.ld, q.ld, Nk * k.ld, k.ld, Nk * v.ld, v.ld, Nq * out.ld,
+                                              out.ld, Nq * dq.ld, dq.ld, Nk * dk.ld, dk.ld, Nk * dv.ld, dv.ld, scale, _stream()), 'attn_bwd_tiled')
         return
     if state[0] == 'fused':
         assert d_out.ld == out.ld
