@@ -185,3 +185,17 @@ def staged_loader(data_loader, args, device=None):
     stager = staging.BatchStager(device, mean, std,
                                  standardize_depth=(0.1, 0.9, 1e-6) if getattr(args, 'standardize_depth', False) else None)
     return staging.StagedLoader(data_loader, stager)
+
+
+def seg_criterion(ignore_index: int = 255):
+    """Replaces ``torch.nn.CrossEntropyLoss(ignore_index=utils.SEG_IGNORE_INDEX)`` (run_finetuning_semseg.py:483): the loss and its
+    gradient from the ConvNeXt head's low-resolution logits, the full-resolution image neither written nor read."""
+    from multimae_amd.criterion import SegCrossEntropyLoss
+    return SegCrossEntropyLoss(ignore_index=ignore_index)
+
+
+def seg_metric(num_classes: int, ignore_index: int = 255, device=None):
+    """Replaces the host-side lists + ``compute_metrics_distributed`` of ``evaluate()`` (run_finetuning_semseg.py): call
+    ``metric.update(seg_pred, seg_gt)`` per batch, then ``metric.sync()`` and ``all_acc, acc, iou = metric.compute()``."""
+    from multimae_amd.metrics import SegMetric
+    return SegMetric(num_classes, ignore_index, device)

@@ -979,6 +979,30 @@ int mmae_dwconv7_wgrad(const float* x, const float* dy, float* part, int B, int 
 int mmae_resize_fwd(const float* x, int64_t ldx, float* out, int B, int h, int w, int K, int H, int W, int mode, void* stream);
 int mmae_resize_bwd(const float* g, float* dx, int64_t ldx, int B, int h, int w, int K, int H, int W, int mode, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Semantic-segmentation loss and metrics on the head's low-resolution logits, csrc/segloss.hip: the (B, K, H, W) image of
+ * mmae_resize_fwd is never read.  x f32 [B][h][w][ldx] (first K columns), target / pred / label int64 [B][H][W], mode as in
+ * mmae_resize_fwd (every geometry it takes is taken here), the interpolated value bit-identical to the pixel it would store.  A target
+ * outside [0, K) counts as ignored, like ignore_index.  No float atomics; results are bit-equal from run to run.
+ *   seg_ce_fwd:  nn.CrossEntropyLoss(ignore_index, reduction='mean') of the interpolated logits.  lse f32 [B][H][W] (log-sum-exp of
+ *                every pixel), partial f32 [2 MMAE_SEG_PARTIALS] (scratch: per-workgroup sum and count), out f32 [2]: out[0] = sum /
+ *                count -- 0 when no pixel is valid --, out[1] = count.  No host synchronisation.
+ *   seg_ce_bwd:  dx f32 [B][h][w][ldx] = up[0] / out[1] * d(sum)/dx, every element summing its output window in a fixed order, softmax
+ *                recomputed from lse; columns K .. ldx - 1 written as zeros.  up: the upstream gradient, one f32 on the device.
+ *   seg_argmax:  pred = argmax over the first n_cls <= K interpolated logits, the lowest index on ties.
+ *   seg_hist:    hist int64 [4][K] += intersection, union, prediction and label histograms (utils/semseg_metrics.py:49-59) of the n
+ *                pixels with label != ignore_index; values outside [0, K) are dropped (np.histogram's closed last bin, which would
+ *                count a value equal to K into class K - 1, is not reproduced).  K <= MMAE_SEG_HIST_MAX_K.
+ * ------------------------------------------------------------------------- */
+#define MMAE_SEG_PARTIALS 2048
+#define MMAE_SEG_HIST_MAX_K 4096
+int mmae_seg_ce_fwd(const float* x, int64_t ldx, const int64_t* target, int64_t ignore_index, int B, int h, int w, int K, int H, int W, int mode,
+                    float* lse, float* partial, float* out, void* stream);
+int mmae_seg_ce_bwd(const float* x, int64_t ldx, const int64_t* target, int64_t ignore_index, int B, int h, int w, int K, int H, int W, int mode,
+                    const float* lse, const float* out, const float* up, float* dx, void* stream);
+int mmae_seg_argmax(const float* x, int64_t ldx, int B, int h, int w, int K, int n_cls, int H, int W, int mode, int64_t* pred, void* stream);
+int mmae_seg_hist(const int64_t* pred, const int64_t* label, int64_t n, int K, int64_t ignore_index, int64_t* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

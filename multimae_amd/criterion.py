@@ -7,14 +7,15 @@ norm_pix uses the unbiased patch variance with eps 1e-6 inside the sqrt.
 
 Deliberate deviation (documented in DESIGN.md): when NO token of the batch is masked the
 reference returns ``torch.tensor(0)`` (int64, after a host sync); this engine returns a float32
-zero with zero gradient and never synchronises.
+zero with zero gradient and never synchronises.  SegCrossEntropyLoss does the same for a batch without
+a valid pixel, where ``nn.CrossEntropyLoss`` returns NaN.
 """
 from __future__ import annotations
 
 import torch
 from torch import nn
 
-from .functions import MaskedCEFn, MaskedCEPatFn, MaskedPixelLossFn, MaskedPixelLossPatFn
+from .functions import MaskedCEFn, MaskedCEPatFn, MaskedPixelLossFn, MaskedPixelLossPatFn, SegCEFn
 from .lazy import materialize as _materialize
 
 
@@ -86,3 +87,29 @@ class MaskedMSELoss(_MaskedPixelLoss):
 class MaskedL1Loss(_MaskedPixelLoss):
     """L1 loss with masking (patch_size, stride, norm_pix)."""
     kind = 1
+
+
+def _seg_handle(x: torch.Tensor):
+    """The ConvNeXt head's low-resolution logits behind prediction x (functions.SegHandle), if x is exactly what the head returned
+    (or a ``clone()`` of it) and has not been modified; None otherwise."""
+    h = getattr(x, '_mmae_seg', None)
+    if h is None or not h.matches(x) or not getattr(x, 'unmodified', True):
+        return None
+    return h
+
+
+class SegCrossEntropyLoss(nn.CrossEntropyLoss):
+    """``nn.CrossEntropyLoss`` (same constructor) for the semantic-segmentation fine-tuning loop (run_finetuning_semseg.py:483).  On a
+    prediction of the ConvNeXt head with an integer target map of the image's size, no class weights, no label smoothing and
+    reduction='mean', the loss and its gradient are computed from the head's low-resolution logits (functions.SegCEFn): the
+    (B, K, H, W) image is neither written nor read.  Anything else is ``nn.CrossEntropyLoss`` on the image itself.  Deviations on
+    the fused path: a target outside [0, K) other than ignore_index counts as ignored (torch: device assert), and a batch without
+    a valid pixel gives 0 with a zero gradient (torch: NaN)."""
+
+    def forward(self, input, target):
+        h = _seg_handle(input)
+        if (h is not None and self.weight is None and self.label_smoothing == 0 and self.reduction == 'mean'
+                and not target.is_floating_point() and not target.is_complex() and target.dtype != torch.bool
+                and tuple(target.shape) == (h.B, h.H, h.W) and target.device == h.logits.device):
+            return SegCEFn.apply(h.token, h, target, int(self.ignore_index))
+        return super().forward(input, target)

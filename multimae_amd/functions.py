@@ -1228,16 +1228,41 @@ CONVNEXT_BLOCK_PARAMS = ('dwconv.weight', 'dwconv.bias', 'norm.weight', 'norm.bi
                          'pwconv2.bias')
 
 
+class SegHandle:
+    """PatHandle's twin for the ConvNeXt head: side channel between the head and a loss or metric evaluated on its prediction.  Holds
+    the head's low-resolution logits (f32 [B h w, ld], channels-last, ld = round_up(K, 8)), the geometry of the F.interpolate that
+    would turn them into the (B, K, H, W) image, the autograd `token` that links the loss node to the head's node, and -- filled in
+    by the loss's backward -- `d_logits`, the gradient with respect to the logits (f32 [B h w, ld], columns K .. ld - 1 zero)."""
+    __slots__ = ('logits', 'token', 'B', 'h', 'w', 'K', 'ld', 'H', 'W', 'mode', 'd_logits')
+
+    def __init__(self, logits, B, h, w, K, ld, H, W, mode):
+        self.logits, self.B, self.h, self.w, self.K, self.ld, self.H, self.W, self.mode = logits, B, h, w, K, ld, H, W, mode
+        self.token, self.d_logits = None, None
+
+    def matches(self, img: Tensor) -> bool:
+        return self.logits is not None and self.token is not None and tuple(img.shape) == (self.B, self.K, self.H, self.W)
+
+    def geom(self):
+        return (self.B, self.h, self.w, self.K, self.H, self.W, self.mode)
+
+
 class ConvNeXtHeadFn(torch.autograd.Function):
     """The whole head as ONE autograd node: token rows -> proj_dec -> pixel shuffle -> depth x ConvNeXtBlock -> final_layer ->
     F.interpolate.  The map is f32 channels-last [B h w, C]; LayerNorm and the 1 x 1 convolutions run on its pixel rows
     (mmae_layernorm_*, mmae_gemm with the bias + GELU' pair and the bias + residual epilogues), the depthwise 7 x 7 convolutions,
     the shuffle and the resize on csrc/convnext.hip.  params: CONVNEXT_BLOCK_PARAMS per block, then final_layer.{weight, bias},
-    proj_dec.{weight, bias}."""
+    proj_dec.{weight, bias}.
+
+    forward returns (image, token).  cfg.handle is the SegHandle of the call (the logits stay alive with it); the token's only purpose
+    is to connect a loss evaluated on the logits (SegCEFn) to this node.  With engine.lazy_predictions() on and no graph capture
+    running the image is allocated but not written: cfg.lazy_fill writes it (mmae_resize_fwd, as the eager path) when somebody
+    reads it (lazy.LazyPrediction, wrapped around the result by ConvNeXtAdapter.forward)."""
 
     @staticmethod
     def forward(ctx, cfg: _Cfg, enc: Tensor, *params: Tensor):
         ops._require_gpu(enc, 'ConvNeXt head input')
+        ctx.set_materialize_grads(False)
+        cfg.handle = cfg.lazy_fill = None
         act, wc = cfg.act, cfg.wc
         B, n_tok, D = enc.shape
         N, NH, NW, s, C, K, H, W, depth = cfg.N, cfg.NH, cfg.NW, cfg.s, cfg.C, cfg.K, cfg.H, cfg.W, cfg.depth
@@ -1265,25 +1290,54 @@ class ConvNeXtHeadFn(torch.autograd.Function):
         xa = ops.cast(x, act)
         logits = _new((R, Kp), enc, f32)
         ops.gemm(xa, wc(fw).view(K, C), logits, R, K, C, lda=C, ldb=C, ldc=Kp, bias=fb.detach())   # final_layer (:566)
-        out = ops.resize_fwd(logits, Kp, _new((B, K, H, W), enc, f32), B, h, w, K, H, W, cfg.mode)  # F.interpolate (:568)
-        ctx.cfg, ctx.params, ctx.saved, ctx.rest = cfg, params, saved, (x_tok, xa, n_tok, D, Kp)
-        return out
+        out = _new((B, K, H, W), enc, f32)
+        geom = (B, h, w, K, H, W, cfg.mode)
+        if engine.lazy_predictions() and engine.capturing() is None:
+            # the image is an API output the fused loss and argmax never read (criterion.SegCrossEntropyLoss, metrics.seg_argmax)
+            ev = torch.cuda.current_stream().record_event() if enc.is_cuda else None
+
+            def fill(dst, logits=logits, ev=ev, geom=geom, Kp=Kp):
+                if ev is not None:
+                    cur = torch.cuda.current_stream()
+                    cur.wait_event(ev)
+                    logits.record_stream(cur)
+                ops.resize_fwd(logits, Kp, dst, *geom)
+            cfg.lazy_fill = fill
+        else:
+            ops.resize_fwd(logits, Kp, out, *geom)                # F.interpolate (:568)
+        token = out.new_empty(1)
+        if engine.patch_domain_loss():
+            cfg.handle = SegHandle(logits, B, h, w, K, Kp, H, W, cfg.mode)
+            cfg.handle.token = token
+        ctx.handle = cfg.handle
+        ctx.cfg, ctx.params, ctx.saved, ctx.rest = cfg, params, saved, (x_tok, xa, n_tok, D, Kp, B)
+        return out, token
 
     @staticmethod
-    def backward(ctx, d_out: Tensor):
+    def backward(ctx, d_out: Optional[Tensor], d_token: Optional[Tensor] = None):
         cfg, params = ctx.cfg, ctx.params
-        x_tok, xa, n_tok, D, Kp = ctx.rest
+        x_tok, xa, n_tok, D, Kp, B = ctx.rest
         act, wc = cfg.act, cfg.wc
         N, NH, NW, s, C, K, H, W, depth = cfg.N, cfg.NH, cfg.NW, cfg.s, cfg.C, cfg.K, cfg.H, cfg.W, cfg.depth
         h, w = NH * s, NW * s
-        B = d_out.shape[0]
         R = B * h * w
         f32 = torch.float32
         sink = GradSink(engine.direct_grads())
         grads: List[Optional[Tensor]] = [None] * len(params)
         fw, fb, pw, pb = params[8 * depth:8 * depth + 4]
-        g = d_out.contiguous().float()
-        d_log = ops.resize_bwd(g, _new((R, Kp), g, f32), Kp, B, h, w, K, H, W, cfg.mode)
+        hd = ctx.handle
+        d_log = hd.d_logits if hd is not None else None          # from a loss on the logits (SegCEFn)
+        if d_log is not None:
+            hd.d_logits = None
+            if xa.is_cuda:
+                d_log.record_stream(torch.cuda.current_stream())
+        if d_out is not None:                                     # somebody used the image itself
+            g = d_out.contiguous().float()
+            d_img = ops.resize_bwd(g, _new((R, Kp), g, f32), Kp, B, h, w, K, H, W, cfg.mode)
+            d_log = d_img if d_log is None else d_log.add_(d_img)
+        elif d_log is None:                                       # nothing reached the head
+            d_log = torch.zeros((R, Kp), device=xa.device, dtype=f32)
+        g = d_log
         d_log = ops.cast(d_log, act)[:, :K]                       # row stride Kp, zero columns K .. Kp - 1
         dx = ops.linear_dx(d_log, wc(fw).view(K, C), _new((R, C), g, f32))
         grads[8 * depth], grads[8 * depth + 1] = sink.linear(fw, fb, d_log, xa)
@@ -1317,3 +1371,29 @@ class ConvNeXtHeadFn(torch.autograd.Function):
         grads[8 * depth + 2], grads[8 * depth + 3] = sink.linear(pw, pb, dp_a, x_tok)
         ctx.saved = ctx.params = ctx.rest = None
         return (None, d_enc, *grads)
+
+
+class SegCEFn(torch.autograd.Function):
+    """nn.CrossEntropyLoss(ignore_index, reduction='mean') on the ConvNeXt head's low-resolution logits (SegHandle): the interpolation
+    happens inside the loss kernels (csrc/segloss.hip), the gradient goes back to the head as d_logits.  A target outside [0, K) counts
+    as ignored; a batch without a valid pixel gives an f32 zero with a zero gradient (torch: NaN)."""
+
+    @staticmethod
+    def forward(ctx, token: Tensor, h: SegHandle, target: Tensor, ignore_index: int):
+        ops._require_gpu(h.logits, 'loss input')
+        target = target.contiguous().long()
+        lse, out = ops.seg_ce_fwd(h.logits, h.ld, target, ignore_index, *h.geom())
+        ctx.saved = (h, target, lse, out, target._version)
+        ctx.ignore_index = int(ignore_index)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        h, target, lse, out, version = ctx.saved
+        ctx.saved = None
+        if target._version != version:
+            raise RuntimeError('a tensor saved for the segmentation-loss backward was modified in place')
+        up = g.contiguous().float().reshape(1)
+        d = ops.seg_ce_bwd(h.logits, h.ld, target, ctx.ignore_index, *h.geom(), lse, out, up, torch.empty_like(h.logits))
+        h.d_logits = d if h.d_logits is None else h.d_logits.add_(d)     # several losses on one prediction: their gradients add
+        return up.new_empty(1), None, None, None

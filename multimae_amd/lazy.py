@@ -73,8 +73,9 @@ class LazyPrediction(torch.Tensor):
         with torch._C.DisableTorchFunctionSubclass():
             new = _LazyCloneFn.apply(self) if fill is not None else torch.Tensor.clone(self)
         out = LazyPrediction.wrap(new, fill)
-        if self.unmodified and hasattr(self, '_mmae_pat'):
-            out._mmae_pat = self._mmae_pat
+        for side in ('_mmae_pat', '_mmae_seg'):        # functions.PatHandle / SegHandle
+            if self.unmodified and hasattr(self, side):
+                setattr(out, side, getattr(self, side))
         return out
 
     @property

@@ -1550,3 +1550,43 @@ def resize_bwd(g: Tensor, dx: Tensor, ldx: int, B: int, h: int, w: int, K: int, 
     """its backward: g f32 [B, K, H, W] -> dx f32 [B, h, w, ldx] (columns K .. ldx - 1 zeroed)"""
     check(_lib.load().mmae_resize_bwd(g.data_ptr(), dx.data_ptr(), ldx, B, h, w, K, H, W, RESIZE_MODES[mode], _stream()), 'resize_bwd')
     return dx
+
+
+# ------------------------------------------------- segmentation loss and metrics on the low-resolution logits (csrc/segloss.hip) --
+SEG_PARTIALS = 2048          # MMAE_SEG_PARTIALS: rows of the forward's per-workgroup (sum, count) scratch
+SEG_HIST_MAX_K = 4096        # MMAE_SEG_HIST_MAX_K
+
+
+def seg_ce_fwd(x: Tensor, ldx: int, target: Tensor, ignore_index: int, B: int, h: int, w: int, K: int, H: int, W: int, mode: str,
+               lse: Optional[Tensor] = None):
+    """CrossEntropyLoss(ignore_index) of the interpolated logits without the image: x f32 [B, h, w, ldx], target int64 [B, H, W] ->
+    (lse f32 [B, H, W], out f32 [2] = (loss, valid-pixel count)); nothing is read back to the host."""
+    if lse is None:
+        lse = torch.empty((B, H, W), device=x.device, dtype=torch.float32)
+    partial = torch.empty((2 * SEG_PARTIALS,), device=x.device, dtype=torch.float32)
+    out = torch.empty((2,), device=x.device, dtype=torch.float32)
+    check(_lib.load().mmae_seg_ce_fwd(x.data_ptr(), ldx, target.data_ptr(), int(ignore_index), B, h, w, K, H, W, RESIZE_MODES[mode],
+                                      lse.data_ptr(), partial.data_ptr(), out.data_ptr(), _stream()), 'seg_ce_fwd')
+    return lse, out
+
+
+def seg_ce_bwd(x: Tensor, ldx: int, target: Tensor, ignore_index: int, B: int, h: int, w: int, K: int, H: int, W: int, mode: str,
+               lse: Tensor, out: Tensor, up: Tensor, dx: Tensor) -> Tensor:
+    """its gradient: dx f32 [B, h, w, ldx] = up / count * d(sum)/dx (columns K .. ldx - 1 zeroed); up f32 [1] on the device"""
+    check(_lib.load().mmae_seg_ce_bwd(x.data_ptr(), ldx, target.data_ptr(), int(ignore_index), B, h, w, K, H, W, RESIZE_MODES[mode],
+                                      lse.data_ptr(), out.data_ptr(), up.data_ptr(), dx.data_ptr(), _stream()), 'seg_ce_bwd')
+    return dx
+
+
+def seg_argmax(x: Tensor, ldx: int, pred: Tensor, B: int, h: int, w: int, K: int, n_cls: int, H: int, W: int, mode: str) -> Tensor:
+    """pred int64 [B, H, W] = argmax over the first n_cls interpolated logits (lowest index on ties)"""
+    check(_lib.load().mmae_seg_argmax(x.data_ptr(), ldx, B, h, w, K, n_cls, H, W, RESIZE_MODES[mode], pred.data_ptr(), _stream()),
+          'seg_argmax')
+    return pred
+
+
+def seg_hist(pred: Tensor, label: Tensor, K: int, ignore_index: int, hist: Tensor) -> Tensor:
+    """hist int64 [4, K] += (intersection, union, prediction, label) histograms of pred / label int64 (same shape, contiguous)"""
+    check(_lib.load().mmae_seg_hist(pred.data_ptr(), label.data_ptr(), pred.numel(), K, int(ignore_index), hist.data_ptr(), _stream()),
+          'seg_hist')
+    return hist

@@ -331,7 +331,16 @@ class ConvNeXtAdapter(nn.Module):
         if cfg.act != torch.float32 and (C % 8 or self.in_channels % 8):
             raise ValueError(f'ConvNeXtAdapter: the bf16 GEMMs need embed_dim / preds_per_patch ({C}) and the concatenated token width '
                              f'({self.in_channels}) to be multiples of 8; use engine.set_precision("fp32") for this geometry')
-        return ConvNeXtHeadFn.apply(cfg, encoder_tokens, *self._params())
+        img, _ = ConvNeXtHeadFn.apply(cfg, encoder_tokens, *self._params())
+        if getattr(cfg, 'lazy_fill', None) is not None or cfg.handle is not None:
+            # written when first read (criterion.SegCrossEntropyLoss and metrics.seg_argmax work on the low-resolution logits and never
+            # read it); already written when the head ran eagerly -- the wrapper then only carries the side channel through clone()
+            from .lazy import LazyPrediction
+            img = LazyPrediction.wrap(img, getattr(cfg, 'lazy_fill', None))
+            cfg.lazy_fill = None
+        if cfg.handle is not None:
+            img._mmae_seg = cfg.handle       # functions.SegHandle: the logits behind exactly this tensor
+        return img
 
 
 class DPTOutputAdapter(nn.Module):
