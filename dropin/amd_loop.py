@@ -20,6 +20,11 @@ hooks (13.4 ms), the 345 ``torch.norm`` calls of ``get_grad_norm_`` (9.9 ms), DD
   create_optimizer(args, model_without_ddp, skip_list=..,       create_optimizer_groups(args, model, ...): FusedAdamW(groups=..)
       get_num_layer=.., get_layer_scale=..)  (fine-tuning,       over the same param groups (no decay for biases / 1-D / skip list,
       run_finetuning_cls.py:386-389, utils/optim_factory.py:21)  layer-wise lr decay), still one fused library call per step
+  Mixup(...), the criterion choice, ModelEma(...)                mixup(args), cls_criterion(args, mixup_fn), model_ema(model, args):
+      run_finetuning_cls.py:299-306, :403-409, :344-352          the batch mixed in place in one launch, the soft-target loss as one
+                                                                 autograd node, the EMA as one launch over two parameter arenas
+  loss_scaler(..., update_grad=False)  (--update_freq > 1)       LossScaler: the backward of an accumulation micro-step runs inside
+      run_finetuning_cls.py:528-531                              reducer.hold() -- gradients are exchanged once per update
 
 The patch that wires them in is ``dropin/run_pretraining_multimae.patch`` (three call sites).  Everything else in the script --
 argument parsing, cosine tables, the per-iteration ``param_group['lr']`` assignment (:474-480), ``train_one_epoch`` itself,
@@ -28,6 +33,7 @@ the bench geometry against the native loop.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import torch
@@ -155,10 +161,14 @@ class LossScaler:
 
     def __call__(self, loss, optimizer: FusedAdamW, clip_grad: Optional[float] = None, skip_grad: Optional[float] = None,
                  parameters=None, create_graph: bool = False, update_grad: bool = True):
-        loss.backward(create_graph=create_graph)
-        if not update_grad:
-            return None
         reducer = getattr(optimizer, '_amd_reducer', None)
+        if not update_grad:
+            # an accumulation micro-step (``--update_freq > 1``): the gradients stay local partial sums -- the reducer neither counts
+            # readiness nor launches a bucket; FusedAdamW.zero_grad() / engine.claim_first_write make the next backward accumulate
+            with (reducer.hold() if reducer is not None else contextlib.nullcontext()):
+                loss.backward(create_graph=create_graph)
+            return None
+        loss.backward(create_graph=create_graph)
         if reducer is not None:
             reducer.finish()
         optimizer.clip_grad, optimizer.skip_grad = clip_grad, skip_grad
@@ -199,3 +209,32 @@ def seg_metric(num_classes: int, ignore_index: int = 255, device=None):
     ``metric.update(seg_pred, seg_gt)`` per batch, then ``metric.sync()`` and ``all_acc, acc, iou = metric.compute()``."""
     from multimae_amd.metrics import SegMetric
     return SegMetric(num_classes, ignore_index, device)
+
+
+def mixup(args):
+    """Replaces the ``Mixup(...)`` construction of run_finetuning_cls.py:299-306: the engine's ``multimae_amd.Mixup`` from the same
+    arguments, or None when ``--mixup``, ``--cutmix`` and ``--cutmix_minmax`` are all off."""
+    active = args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None
+    if not active:
+        return None
+    return M.Mixup(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
+                   switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, label_smoothing=args.smoothing,
+                   num_classes=args.nb_classes)
+
+
+def cls_criterion(args, mixup_fn=None):
+    """Replaces the criterion choice of run_finetuning_cls.py:403-409: soft targets under mixup (the smoothing is in the target),
+    label smoothing without it, plain cross-entropy (``torch.nn.CrossEntropyLoss``, as the script) when both are off."""
+    if mixup_fn is not None:
+        return M.SoftTargetCrossEntropy()
+    if args.smoothing > 0.:
+        return M.LabelSmoothingCrossEntropy(smoothing=args.smoothing)
+    return torch.nn.CrossEntropyLoss()
+
+
+def model_ema(model: torch.nn.Module, args=None, decay: Optional[float] = None):
+    """Replaces ``ModelEma(model, decay=args.model_ema_decay, device=..., resume='')`` (run_finetuning_cls.py:344-352): the engine's
+    ``multimae_amd.ModelEma``, one launch per update.  ``--model_ema_force_cpu`` is not supported (NotImplementedError)."""
+    if decay is None:
+        decay = getattr(args, 'model_ema_decay', 0.9999)
+    return M.ModelEma(model, decay=decay, device='cpu' if getattr(args, 'model_ema_force_cpu', False) else '', resume='')

@@ -1003,6 +1003,43 @@ int mmae_seg_ce_bwd(const float* x, int64_t ldx, const int64_t* target, int64_t 
 int mmae_seg_argmax(const float* x, int64_t ldx, int B, int h, int w, int K, int n_cls, int H, int W, int mode, int64_t* pred, void* stream);
 int mmae_seg_hist(const int64_t* pred, const int64_t* label, int64_t n, int K, int64_t ignore_index, int64_t* hist, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * The classification fine-tuning recipe (run_finetuning_cls.py: --mixup / --cutmix / --smoothing / --model_ema), csrc/clsrecipe.hip.
+ * No float atomics; results are bit-equal from run to run.  mixup_pairs, mix_target and ema_update are bit-identical to the
+ * reference's eager f32 expressions (every product and sum rounds on its own: no FMA contraction).
+ *
+ * rows: the per-sample parameter block, B rows of MMAE_MIX_ROW_WORDS 32-bit words on the device:
+ *     f32 w_self, w_other   blend weights of the pixels          out = fl(fl(self w_self) + fl(other w_other))
+ *     f32 t_self, t_other   blend weights of the target rows     (lam and 1 - lam as the reference's mode forms them)
+ *     i32 yl, yh, xl, xh    CutMix box: inside out = other, outside out = self.  yl == MMAE_MIX_BLEND: no box, blend;
+ *                           yl == MMAE_MIX_KEEP: the sample is not written at all (lam == 1: the reference skips it)
+ *   "other" of sample i is sample B - 1 - i (x.flip(0)).  The host expands the reference's three modes into rows.
+ *   mixup_pairs: Mixup._mix_batch / _mix_pair / _mix_elem (utils/mixup.py:166-214) on x f32 [B][C][H][W] in place, B even: one work
+ *                item holds the same pixels of samples i and B - 1 - i, so both read the other's ORIGINAL values (x_orig / x.flip(0))
+ *                without a clone.  16-byte accesses when W % 4 == 0 and x is 16-byte aligned, element-wise otherwise.
+ *   mix_target:  mixup_target (utils/mixup.py:23-33): target f32 [B][K] = fl(fl(y1 t_self) + fl(y2 t_other)), y1 / y2 the rows
+ *                (on_value at the label, off_value elsewhere) of labels[i] / labels[B - 1 - i].  The caller checks the labels' range.
+ *   soft_ce_fwd: SoftTargetCrossEntropy (target f32 [B][K] dense, labels NULL) or LabelSmoothingCrossEntropy (target NULL, labels int64
+ *                [B], t_k = smoothing / K + (1 - smoothing) [k == label]) of x [B][ldx] (first K columns), x_dtype MMAE_F32 or MMAE_BF16
+ *                (utils/cross_entropy.py:17-43).  lse, tsum, rowloss f32 [B]: log-sum-exp, sum_k t_k (1 for the label form) and
+ *                sum_k t_k (lse - x_k) of every row; out f32 [1] = mean of rowloss, summed in a fixed tree.  No host synchronisation.
+ *   soft_ce_bwd: dx [B][ldx] (x's dtype) = up[0] / B * (exp(x - lse) tsum - t); columns K .. ldx - 1 written as zeros.  up: the
+ *                upstream gradient, one f32 on the device.
+ *   ema_update:  ModelEma.update (utils/model_ema.py:72-83) over two flat f32 arrays of n elements: ema[i] = fl(fl(ema[i] decay) +
+ *                fl(one_minus_decay p[i])); shadow (bf16 [n], may be NULL) receives the rounded new value in the same launch.
+ *                16-byte accesses when n % 4 == 0 and the pointers are aligned.
+ * ------------------------------------------------------------------------- */
+#define MMAE_MIX_ROW_WORDS 8
+#define MMAE_MIX_BLEND (-1)
+#define MMAE_MIX_KEEP (-2)
+int mmae_mixup_pairs(float* x, const void* rows, int B, int C, int H, int W, void* stream);
+int mmae_mix_target(const int64_t* labels, const void* rows, float* target, int B, int K, float on_value, float off_value, void* stream);
+int mmae_soft_ce_fwd(const void* x, int x_dtype, int64_t ldx, const float* target, const int64_t* labels, float smoothing, int B, int K,
+                     float* lse, float* tsum, float* rowloss, float* out, void* stream);
+int mmae_soft_ce_bwd(const void* x, int x_dtype, int64_t ldx, const float* target, const int64_t* labels, float smoothing, int B, int K,
+                     const float* lse, const float* tsum, const float* up, void* dx, void* stream);
+int mmae_ema_update(float* ema, const float* p, void* shadow, int64_t n, float decay, float one_minus_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

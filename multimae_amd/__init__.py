@@ -7,7 +7,10 @@ data-parallel gradient reducer) and the batch stager (host batches copied on the
 """
 from . import engine  # noqa: F401
 from .data_ops import truncated_depth_standardize  # noqa: F401
-from .criterion import MaskedCrossEntropyLoss, MaskedL1Loss, MaskedMSELoss, SegCrossEntropyLoss  # noqa: F401
+from .criterion import (LabelSmoothingCrossEntropy, MaskedCrossEntropyLoss, MaskedL1Loss, MaskedMSELoss,  # noqa: F401
+                        SegCrossEntropyLoss, SoftTargetCrossEntropy)
+from .ema import ModelEma  # noqa: F401
+from .mixup import Mixup  # noqa: F401
 from .metrics import SegMetric, seg_argmax  # noqa: F401
 from .input_adapters import PatchedInputAdapter, SemSegInputAdapter  # noqa: F401
 from .multimae import (MultiMAE, MultiViT, multivit_base, multivit_large,  # noqa: F401

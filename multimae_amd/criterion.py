@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .functions import MaskedCEFn, MaskedCEPatFn, MaskedPixelLossFn, MaskedPixelLossPatFn, SegCEFn
+from .functions import MaskedCEFn, MaskedCEPatFn, MaskedPixelLossFn, MaskedPixelLossPatFn, SegCEFn, SoftCEFn
 from .lazy import materialize as _materialize
 
 
@@ -113,3 +113,42 @@ class SegCrossEntropyLoss(nn.CrossEntropyLoss):
                 and tuple(target.shape) == (h.B, h.H, h.W) and target.device == h.logits.device):
             return SegCEFn.apply(h.token, h, target, int(self.ignore_index))
         return super().forward(input, target)
+
+
+def _cls_logits(x) -> torch.Tensor:
+    if not (torch.is_tensor(x) and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16)):
+        raise ValueError('classification loss: the input is a (B, K) tensor of float32 or bfloat16 logits')
+    return x
+
+
+class SoftTargetCrossEntropy(nn.Module):
+    """``utils.SoftTargetCrossEntropy`` (utils/cross_entropy.py:36-43) for the classification fine-tuning loop: mean over the batch of
+    ``sum_k -target_k log_softmax(x)_k`` on logits (B, K) and a dense float32 target (B, K) -- what ``Mixup`` returns.  One autograd
+    node (functions.SoftCEFn): the forward saves the rows' log-sum-exp, the backward recomputes the softmax from it."""
+
+    def forward(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        x = _cls_logits(x)
+        if not (torch.is_tensor(target) and target.dtype == torch.float32 and tuple(target.shape) == tuple(x.shape)):
+            raise ValueError(f'SoftTargetCrossEntropy: the target is a float32 tensor of the logits\' shape {tuple(x.shape)} '
+                             '(class probabilities, as Mixup returns them)')
+        return SoftCEFn.apply(x, target.to(x.device).contiguous(), None, 0.0)
+
+
+class LabelSmoothingCrossEntropy(nn.Module):
+    """``utils.LabelSmoothingCrossEntropy`` (utils/cross_entropy.py:17-33): ``(1 - smoothing) nll + smoothing mean_k(-log_softmax)`` on
+    logits (B, K) and int64 class indices (B,), mean over the batch.  Same kernels as SoftTargetCrossEntropy, the target row
+    ``smoothing / K + (1 - smoothing) [k == label]`` formed on the fly.  A label outside [0, K) contributes the smoothing term only
+    (torch: device assert in the gather)."""
+
+    def __init__(self, smoothing: float = 0.1):
+        super().__init__()
+        if not smoothing < 1.0:
+            raise ValueError('LabelSmoothingCrossEntropy: smoothing must be below 1')
+        self.smoothing = smoothing
+        self.confidence = 1. - smoothing
+
+    def forward(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        x = _cls_logits(x)
+        if not (torch.is_tensor(target) and target.dtype == torch.int64 and tuple(target.shape) == (x.shape[0],)):
+            raise ValueError(f'LabelSmoothingCrossEntropy: the target is an int64 tensor of {x.shape[0]} class indices')
+        return SoftCEFn.apply(x, None, target.to(x.device).contiguous(), float(self.smoothing))

@@ -24,6 +24,7 @@ Backend-agnostic (torch.distributed): "nccl" == RCCL on ROCm; the gloo CPU tests
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
@@ -106,6 +107,7 @@ class GradAllReducer:
         self._events: List[list] = []
         self._launch_stream = None
         self._side_of = None
+        self._held = 0
         self.reset()
 
     @classmethod
@@ -211,9 +213,23 @@ class GradAllReducer:
         self._handles.append((h, i))
 
     # -- readiness ----------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def hold(self):
+        """A backward pass that is NOT the step's last one (gradient accumulation, ``--update_freq > 1``): inside, readiness reports
+        neither count nor launch anything -- the gradients they announce are still local partial sums that the next micro-batch
+        adds to.  The last micro-batch's backward runs outside the hold and reports every parameter again, so its buckets launch as
+        they complete and overlap that backward as in a step without accumulation; finish() reduces whatever never reported."""
+        self._held += 1
+        try:
+            yield self
+        finally:
+            self._held -= 1
+
     def mark_ready(self, names: List[str]) -> None:
         """The gradients of these parameters are final (written by kernels already enqueued on the current stream or its
         side stream): launch every bucket that became complete."""
+        if self._held > 0:
+            return                                       # an accumulation micro-step: nothing is final yet (hold())
         if not self.direct_grads():
             return                                       # autograd still has to deliver them: finish() reduces everything
         touched, done = set(), []

@@ -1397,3 +1397,32 @@ class SegCEFn(torch.autograd.Function):
         d = ops.seg_ce_bwd(h.logits, h.ld, target, ctx.ignore_index, *h.geom(), lse, out, up, torch.empty_like(h.logits))
         h.d_logits = d if h.d_logits is None else h.d_logits.add_(d)     # several losses on one prediction: their gradients add
         return up.new_empty(1), None, None, None
+
+
+class SoftCEFn(torch.autograd.Function):
+    """SoftTargetCrossEntropy (dense f32 target [B, K]) or LabelSmoothingCrossEntropy (int64 labels [B] + smoothing) of the classification
+    head's logits [B, K], f32 or bf16 (csrc/clsrecipe.hip): forward and backward are one launch each, the gradient comes back in the
+    logits' dtype.  Exactly one of target / labels is given."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, target: Optional[Tensor], labels: Optional[Tensor], smoothing: float):
+        ops._require_gpu(x, 'loss input')
+        x = x.contiguous()
+        B, K = x.shape
+        t = target if target is not None else labels
+        lse, tsum, out = ops.soft_ce_fwd(x, K, B, K, target, labels, smoothing)
+        ctx.saved = (x, target, labels, lse, tsum, x._version, t._version)
+        ctx.smoothing = float(smoothing)
+        return out[0]                                # a view of this call's own scratch: no copy launch
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, target, labels, lse, tsum, xv, tv = ctx.saved
+        ctx.saved = None
+        t = target if target is not None else labels
+        if x._version != xv or t._version != tv:
+            raise RuntimeError('a tensor saved for the soft-target loss backward was modified in place')
+        B, K = x.shape
+        up = g.contiguous().float().reshape(1)
+        dx = ops.soft_ce_bwd(x, K, B, K, target, labels, ctx.smoothing, lse, tsum, up, torch.empty_like(x))
+        return dx, None, None, None

@@ -1590,3 +1590,54 @@ def seg_hist(pred: Tensor, label: Tensor, K: int, ignore_index: int, hist: Tenso
     check(_lib.load().mmae_seg_hist(pred.data_ptr(), label.data_ptr(), pred.numel(), K, int(ignore_index), hist.data_ptr(), _stream()),
           'seg_hist')
     return hist
+
+
+# ------------------------------------------------- classification fine-tuning recipe (csrc/clsrecipe.hip) --------------------------
+MIX_ROW_WORDS = 8            # MMAE_MIX_ROW_WORDS: w_self, w_other, t_self, t_other (f32), yl, yh, xl, xh (i32) per sample
+MIX_BLEND, MIX_KEEP = -1, -2  # MMAE_MIX_BLEND / MMAE_MIX_KEEP in the yl word: blend without a box / sample not written
+
+
+def mixup_pairs(x: Tensor, rows: Tensor) -> Tensor:
+    """Mixup._mix_batch / _mix_pair / _mix_elem on x f32 [B, C, H, W] in place from the per-sample block rows int32 [B, 8]"""
+    B, C, H, W = x.shape
+    check(_lib.load().mmae_mixup_pairs(x.data_ptr(), rows.data_ptr(), B, C, H, W, _stream()), 'mixup_pairs')
+    return x
+
+
+def mix_target(labels: Tensor, rows: Tensor, K: int, on_value: float, off_value: float, out: Optional[Tensor] = None) -> Tensor:
+    """mixup_target: labels int64 [B] + the block's target weights -> f32 [B, K]"""
+    B = labels.numel()
+    if out is None:
+        out = torch.empty((B, K), device=labels.device, dtype=torch.float32)
+    check(_lib.load().mmae_mix_target(labels.data_ptr(), rows.data_ptr(), out.data_ptr(), B, K, float(on_value), float(off_value), _stream()),
+          'mix_target')
+    return out
+
+
+def soft_ce_fwd(x: Tensor, ldx: int, B: int, K: int, target: Optional[Tensor], labels: Optional[Tensor], smoothing: float,
+                lse: Optional[Tensor] = None):
+    """Soft-target (dense target f32 [B, K]) or label-smoothing (labels int64 [B]) cross-entropy of x [B, ldx] f32 / bf16 ->
+    (lse, tsum f32 [B], out f32 [1] = mean loss); nothing is read back to the host."""
+    ws = torch.empty((3 * B + 1,), device=x.device, dtype=torch.float32)          # one allocation: tsum, row losses, out (+ lse)
+    tsum, rowloss, out = ws[:B], ws[B:2 * B], ws[3 * B:]
+    if lse is None:
+        lse = ws[2 * B:3 * B]
+    check(_lib.load().mmae_soft_ce_fwd(x.data_ptr(), dcode(x.dtype), ldx, _p(target), _p(labels), float(smoothing), B, K, lse.data_ptr(),
+                                       tsum.data_ptr(), rowloss.data_ptr(), out.data_ptr(), _stream()), 'soft_ce_fwd')
+    return lse, tsum, out
+
+
+def soft_ce_bwd(x: Tensor, ldx: int, B: int, K: int, target: Optional[Tensor], labels: Optional[Tensor], smoothing: float, lse: Tensor,
+                tsum: Tensor, up: Tensor, dx: Tensor) -> Tensor:
+    """its gradient: dx [B, ldx] in x's dtype = up / B * (softmax * tsum - t), columns K .. ldx - 1 zeroed; up f32 [1] on the device"""
+    check(_lib.load().mmae_soft_ce_bwd(x.data_ptr(), dcode(x.dtype), ldx, _p(target), _p(labels), float(smoothing), B, K, lse.data_ptr(),
+                                       tsum.data_ptr(), up.data_ptr(), dx.data_ptr(), _stream()), 'soft_ce_bwd')
+    return dx
+
+
+def ema_update(ema: Tensor, p: Tensor, decay: float, shadow: Optional[Tensor] = None) -> Tensor:
+    """ModelEma.update over two flat f32 arenas: ema = ema * f32(decay) + f32(1. - decay) * p (the difference in double, each product and
+    the sum rounded on its own); shadow bf16 [n] receives the new values in the same launch"""
+    check(_lib.load().mmae_ema_update(ema.data_ptr(), p.data_ptr(), _p(shadow), ema.numel(), float(decay), float(1. - decay), _stream()),
+          'ema_update')
+    return ema
