@@ -211,6 +211,31 @@ def seg_metric(num_classes: int, ignore_index: int = 255, device=None):
     return SegMetric(num_classes, ignore_index, device)
 
 
+def depth_criterion(loss_name: str = 'berhu'):
+    """Replaces the ``tasks_loss_fn`` choice of run_finetuning_depth.py (``--loss l1 | berhu``; ``mse`` is offered as well):
+    ``{'depth': fn}`` with the engine's masked loss, evaluated on the ConvNeXt head's low-resolution map without a host
+    synchronisation (``--output_adapter convnext``)."""
+    from multimae_amd import criterion
+    fns = {'l1': criterion.masked_l1_loss, 'berhu': criterion.masked_berhu_loss, 'mse': criterion.masked_mse_loss}
+    if loss_name not in fns:
+        raise ValueError(f'depth_criterion: loss {loss_name!r} is not one of {sorted(fns)}')
+    return {'depth': fns[loss_name]}
+
+
+def taskonomy_criterion(tasks):
+    """Replaces ``tasks_loss_fn = {task: masked_l1_loss for task in args.out_domains}`` of run_finetuning_taskonomy.py."""
+    from multimae_amd.criterion import masked_l1_loss
+    return {task: masked_l1_loss for task in tasks}
+
+
+def depth_metric(device=None):
+    """Replaces ``masked_nyu_metrics`` + ``metric_logger.update(**metrics)`` in the training loop and ``evaluate()`` of
+    run_finetuning_depth.py: call ``metric.update(preds['depth'], target, mask_valid, loss=loss)`` per batch, then ``metric.sync()``
+    and ``metric.compute()`` -- the only read-back -- for MetricLogger's ``global_avg`` of every value."""
+    from multimae_amd.metrics import DepthMetric
+    return DepthMetric(device)
+
+
 def mixup(args):
     """Replaces the ``Mixup(...)`` construction of run_finetuning_cls.py:299-306: the engine's ``multimae_amd.Mixup`` from the same
     arguments, or None when ``--mixup``, ``--cutmix`` and ``--cutmix_minmax`` are all off."""

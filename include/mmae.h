@@ -1004,6 +1004,36 @@ int mmae_seg_argmax(const float* x, int64_t ldx, int B, int h, int w, int K, int
 int mmae_seg_hist(const int64_t* pred, const int64_t* label, int64_t n, int K, int64_t ignore_index, int64_t* hist, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Dense regression losses and depth metrics on the head's low-resolution map, csrc/regloss.hip: the (B, K, H, W) image of
+ * mmae_resize_fwd is never read.  x f32 [B][h][w][ldx] (first K columns; the others are never read), target f32 [B][K][H][W], mask
+ * one byte per element (torch.bool) [B][mask_channels][H][W] with mask_channels 1 (broadcast over the channels) or K, or NULL
+ * (everything valid); mode as in mmae_resize_fwd, the interpolated value bit-identical to the pixel it would store.
+ * K <= MMAE_REG_MAX_K.  No float atomics; results are bit-equal from run to run; no host synchronisation.
+ *   reg_loss_fwd:   masked_l1_loss / masked_mse_loss / masked_berhu_loss (run_finetuning_depth.py:49-84), kind 0 / 1 / 2.  diff f32
+ *                   [B][K][H][W] = prediction - target, 0 where the mask is false; partial f32 [4 MMAE_REG_PARTIALS] (scratch);
+ *                   out f32 [4] = loss, count of valid elements (stored as f32: exact up to 2^24, rounded to nearest above --
+ *                   berHu's division and the backward's scale use the stored value, a relative 6e-8), max |diff|,
+ *                   c = max(0.2f max|diff|, 1e-5f).  L1: sum |d| / count,
+ *                   MSE: sum d^2 / count, berHu: (sum of |d| where |d| < c and of (d^2 + c^2) / 2 / c elsewhere) / count.  count == 0:
+ *                   loss 0 (the reference: NaN).
+ *   reg_loss_bwd:   dx f32 [B][h][w][ldx] = up[0] / out[1] * d(sum)/dx from diff and out of the forward, every element summing its
+ *                   output window in a fixed order; columns K .. ldx - 1 written as zeros.  d|d| / dd at 0 is 0; berHu's c is a
+ *                   constant.  up: the upstream gradient, one f32 on the device.
+ *   depth_metrics:  masked_nyu_metrics (run_finetuning_depth.py:86-117) for K = 1 with p = x std + mean, t = target std + mean:
+ *                   out f32 [7] = rmse, rel, srel, log10 (the natural log, as there), delta_1, delta_2, delta_3; NaN when nothing
+ *                   is valid, as there.  partial f32 [8 MMAE_REG_PARTIALS] (scratch).  acc f32 [8] or NULL: acc[0..6] += out,
+ *                   acc[7] += 1.
+ * ------------------------------------------------------------------------- */
+#define MMAE_REG_PARTIALS 2048
+#define MMAE_REG_MAX_K 16
+int mmae_reg_loss_fwd(const float* x, int64_t ldx, const float* target, const void* mask, int mask_channels, int kind, int B, int h, int w, int K,
+                      int H, int W, int mode, float* diff, float* partial, float* out, void* stream);
+int mmae_reg_loss_bwd(const float* diff, const float* out, const float* up, int kind, int B, int h, int w, int K, int H, int W, int mode,
+                      float* dx, int64_t ldx, void* stream);
+int mmae_depth_metrics(const float* x, int64_t ldx, const float* target, const void* mask, float mean, float std, int B, int h, int w, int H, int W,
+                       int mode, float* partial, float* out, float* acc, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The classification fine-tuning recipe (run_finetuning_cls.py: --mixup / --cutmix / --smoothing / --model_ema), csrc/clsrecipe.hip.
  * No float atomics; results are bit-equal from run to run.  mixup_pairs, mix_target and ema_update are bit-identical to the
  * reference's eager f32 expressions (every product and sum rounds on its own: no FMA contraction).

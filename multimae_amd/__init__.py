@@ -8,10 +8,10 @@ data-parallel gradient reducer) and the batch stager (host batches copied on the
 from . import engine  # noqa: F401
 from .data_ops import truncated_depth_standardize  # noqa: F401
 from .criterion import (LabelSmoothingCrossEntropy, MaskedCrossEntropyLoss, MaskedL1Loss, MaskedMSELoss,  # noqa: F401
-                        SegCrossEntropyLoss, SoftTargetCrossEntropy)
+                        SegCrossEntropyLoss, SoftTargetCrossEntropy, masked_berhu_loss, masked_l1_loss, masked_mse_loss)
 from .ema import ModelEma  # noqa: F401
 from .mixup import Mixup  # noqa: F401
-from .metrics import SegMetric, seg_argmax  # noqa: F401
+from .metrics import DepthMetric, SegMetric, depth_metrics, seg_argmax  # noqa: F401
 from .input_adapters import PatchedInputAdapter, SemSegInputAdapter  # noqa: F401
 from .multimae import (MultiMAE, MultiViT, multivit_base, multivit_large,  # noqa: F401
                        pretrain_multimae_base, pretrain_multimae_large)

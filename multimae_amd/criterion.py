@@ -8,14 +8,16 @@ norm_pix uses the unbiased patch variance with eps 1e-6 inside the sqrt.
 Deliberate deviation (documented in DESIGN.md): when NO token of the batch is masked the
 reference returns ``torch.tensor(0)`` (int64, after a host sync); this engine returns a float32
 zero with zero gradient and never synchronises.  SegCrossEntropyLoss does the same for a batch without
-a valid pixel, where ``nn.CrossEntropyLoss`` returns NaN.
+a valid pixel, where ``nn.CrossEntropyLoss`` returns NaN, and masked_l1_loss / masked_mse_loss / masked_berhu_loss for a mask without a
+valid element on their fused path, where the reference divides 0 by 0.
 """
 from __future__ import annotations
 
 import torch
 from torch import nn
 
-from .functions import MaskedCEFn, MaskedCEPatFn, MaskedPixelLossFn, MaskedPixelLossPatFn, SegCEFn, SoftCEFn
+from . import engine, ops
+from .functions import MaskedCEFn, MaskedCEPatFn, MaskedPixelLossFn, MaskedPixelLossPatFn, RegLossFn, SegCEFn, SoftCEFn
 from .lazy import materialize as _materialize
 
 
@@ -113,6 +115,100 @@ class SegCrossEntropyLoss(nn.CrossEntropyLoss):
                 and tuple(target.shape) == (h.B, h.H, h.W) and target.device == h.logits.device):
             return SegCEFn.apply(h.token, h, target, int(self.ignore_index))
         return super().forward(input, target)
+
+
+# ------------------------------------------------------------------------------------------
+# Dense regression fine-tuning (run_finetuning_depth.py:49-84, also used by run_finetuning_taskonomy.py)
+# ------------------------------------------------------------------------------------------
+def _reg_fused_ok(h, preds: torch.Tensor, target, mask_valid) -> bool:
+    """The conditions of the fused regression path: the head's own prediction with at most ops.REG_MAX_K channels, an f32 target of
+    its shape on its device, and no mask or a torch.bool mask [B, 1 or K, H, W] on that device."""
+    if h is None or h.K > ops.REG_MAX_K or not torch.is_tensor(target):
+        return False
+    dev = h.logits.device
+    if target.dtype != torch.float32 or tuple(target.shape) != tuple(preds.shape) or target.device != dev:
+        return False
+    if mask_valid is None:
+        return True
+    return (torch.is_tensor(mask_valid) and mask_valid.dtype == torch.bool and mask_valid.device == dev and mask_valid.dim() == 4
+            and mask_valid.shape[1] in (1, h.K) and (mask_valid.shape[0],) + tuple(mask_valid.shape[2:]) == (h.B, h.H, h.W))
+
+
+def _valid_like(preds: torch.Tensor, mask_valid):
+    """the mask in the prediction's shape (one channel is repeated over the channels, as the reference's repeat_interleave) as
+    torch.bool (non-zero = valid); None = all"""
+    if mask_valid is None:
+        return None
+    if mask_valid.dtype != torch.bool:
+        mask_valid = mask_valid.bool()
+    if mask_valid.shape[1] != preds.shape[1]:
+        mask_valid = mask_valid.repeat_interleave(preds.shape[1], 1)
+    return mask_valid
+
+
+def _reg_loss_eager(preds: torch.Tensor, target: torch.Tensor, mask_valid, kind: str) -> torch.Tensor:
+    """The three formulas on the image itself, for everything the fused path does not take.  sum(e(d)) / count with d = preds - target
+    set to 0 where the mask is false: e = |d| (l1), d^2 (mse), or berHu's |d| below c = max(0.2 max|d|, 1e-5) and (d^2 + c^2) / (2 c) from
+    c on, c a constant of the graph.  Written with torch.where, so nothing is read back to the host; an empty mask gives 0 / 0 = NaN, as
+    the reference does."""
+    valid = _valid_like(preds, mask_valid)
+    d = preds - target                                       # reads -- and so writes -- a lazy prediction
+    if valid is None:
+        count = d.numel()
+    else:
+        d = torch.where(valid, d, torch.zeros((), dtype=d.dtype, device=d.device))
+        count = valid.sum()
+    a = d.abs()
+    if kind == 'l1':
+        e = a
+    elif kind == 'mse':
+        e = d * d
+    else:
+        with torch.no_grad():
+            c = (a.max() * 0.2).clamp_min(1e-5)
+        e = torch.where(a < c, a, (d * d + c * c) / 2. / c)
+    return e.sum() / count
+
+
+def _refuse_under_capture(pred, what: str) -> None:
+    """Capturing a step of the ConvNeXt head with a regression loss or the depth metrics -- in graph.StepGraph or a plain
+    torch.cuda.graph -- is unsupported and untested: the one attempt ended in a fault of the runtime when the capture ended, and its
+    cause is not known.  Refused for every prediction that carries the head's side channel, whichever path it would take."""
+    if getattr(pred, '_mmae_seg', None) is None:
+        return
+    if engine.capturing() is not None or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+        raise RuntimeError(f'{what}: capturing a ConvNeXt-head + regression-loss / depth-metrics step in a graph is unsupported and '
+                           'untested; run this step uncaptured')
+
+
+def _reg_loss(preds, target, mask_valid, kind: str) -> torch.Tensor:
+    _refuse_under_capture(preds, f'masked_{kind}_loss')
+    h = _seg_handle(preds)
+    if _reg_fused_ok(h, preds, target, mask_valid):
+        return RegLossFn.apply(h.token, h, target, mask_valid, kind)
+    return _reg_loss_eager(preds, target, mask_valid, kind)
+
+
+def masked_l1_loss(preds, target, mask_valid=None):
+    """``masked_l1_loss`` of run_finetuning_depth.py:59-66: mean |preds - target| over the valid elements.  On an unmodified f32
+    prediction of the ConvNeXt head (``preds[task].float()`` is the same object) with an f32 target of its shape and a torch.bool mask
+    of 1 or K channels, the loss and its gradient come from the head's low-resolution map (functions.RegLossFn) and the image is
+    neither written nor read; a mask without a valid element then gives 0 with a zero gradient (the reference: NaN).  Anything else --
+    a modified prediction, more than 16 channels, a CPU tensor -- is evaluated on the image.  Not inside a graph capture: a head
+    prediction met while a graph.StepGraph or torch.cuda.graph capture runs raises RuntimeError (_refuse_under_capture)."""
+    return _reg_loss(preds, target, mask_valid, 'l1')
+
+
+def masked_mse_loss(preds, target, mask_valid=None):
+    """``masked_mse_loss`` of run_finetuning_depth.py:49-56: mean (preds - target)^2 over the valid elements; paths as masked_l1_loss."""
+    return _reg_loss(preds, target, mask_valid, 'mse')
+
+
+def masked_berhu_loss(preds, target, mask_valid=None):
+    """``masked_berhu_loss`` of run_finetuning_depth.py:69-84: |d| below c = max(0.2 max|d|, 1e-5), (d^2 + c^2) / (2 c) from c on, mean
+    over the valid elements; c is a constant of the graph and never leaves the device (the reference takes a Python ``max()`` of it and
+    indexes with boolean masks: three host synchronisations).  Paths as masked_l1_loss."""
+    return _reg_loss(preds, target, mask_valid, 'berhu')
 
 
 def _cls_logits(x) -> torch.Tensor:

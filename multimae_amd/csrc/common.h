@@ -229,4 +229,21 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- the bilinear resize's four-tap combination (csrc/convnext.hip resize_fwd_kernel; csrc/regloss.hip) -------------------------
+// ly0 (lx0 a + lx1 b) + ly1 (lx0 c + lx1 d) for the taps a, b (row i0 at columns i0, i1) and c, d (row i1), with every rounding
+// fixed: explicit FMAs, contraction off.  Every reader of the head's low-resolution map that promises "the pixel mmae_resize_fwd
+// stores, bit for bit" calls this one function.  The two chains are the ones the resize kernel's four-pixels-per-thread body was
+// compiled to before the roundings were written out (pixels packed in pairs, the even and the odd output column of a pair contracted
+// differently), so the images it writes kept their bits; `odd` is the parity of the output column.
+__device__ __forceinline__ float resize_tap4(float ly0, float ly1, float lx0, float lx1, float a, float b, float c, float d, bool odd) {
+#pragma clang fp contract(off)
+    const float bot = __builtin_fmaf(lx0, c, lx1 * d);
+    if (odd) {
+        const float top = __builtin_fmaf(lx1, b, lx0 * a);
+        return __builtin_fmaf(ly0, top, ly1 * bot);
+    }
+    const float top = __builtin_fmaf(lx0, a, lx1 * b);
+    return __builtin_fmaf(ly1, bot, ly0 * top);
+}
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

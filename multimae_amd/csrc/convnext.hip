@@ -278,8 +278,9 @@ __global__ void __launch_bounds__(256) resize_fwd_kernel(const float* __restrict
             for (int q = 0; q < 4; ++q) {
                 const int ox = oq * 4 + q < W ? oq * 4 + q : W - 1;
                 const Src rx = src_bilinear(ox, sx, w);
-                v[q] = ry.l0 * (rx.l0 * r0[rx.i0 * ldx] + rx.l1 * r0[rx.i1 * ldx]) +
-                       ry.l1 * (rx.l0 * r1[rx.i0 * ldx] + rx.l1 * r1[rx.i1 * ldx]);
+                // ry.l0 (rx.l0 a + rx.l1 b) + ry.l1 (rx.l0 c + rx.l1 d) with its roundings fixed (common.h): ox = 4 oq + q has q's parity
+                v[q] = resize_tap4(ry.l0, ry.l1, rx.l0, rx.l1, r0[rx.i0 * ldx], r0[rx.i1 * ldx], r1[rx.i0 * ldx], r1[rx.i1 * ldx],
+                                   (q & 1) != 0);
             }
         } else {
             const float* r0 = xb + (long long)src_nearest(oy, sy, h) * w * ldx;

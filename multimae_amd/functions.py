@@ -1399,6 +1399,35 @@ class SegCEFn(torch.autograd.Function):
         return up.new_empty(1), None, None, None
 
 
+class RegLossFn(torch.autograd.Function):
+    """masked_l1_loss / masked_mse_loss / masked_berhu_loss (run_finetuning_depth.py:49-84; kind 'l1' / 'mse' / 'berhu') on the ConvNeXt
+    head's low-resolution map (SegHandle): the interpolation happens inside the loss kernels (csrc/regloss.hip), the gradient goes back
+    to the head as d_logits.  mask: torch.bool [B, 1 or K, H, W] or None.  A batch without a valid element gives an f32 zero with a
+    zero gradient (the reference: NaN).  No host synchronisation: berHu's threshold stays on the device."""
+
+    @staticmethod
+    def forward(ctx, token: Tensor, h: SegHandle, target: Tensor, mask: Optional[Tensor], kind: str):
+        ops._require_gpu(h.logits, 'loss input')
+        target = target.contiguous()
+        if mask is not None:
+            mask = mask.contiguous()
+        diff, out = ops.reg_loss_fwd(h.logits, h.ld, target, mask, kind, *h.geom())
+        ctx.saved = (h, target, diff, out, target._version)
+        ctx.kind = kind
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        h, target, diff, out, version = ctx.saved
+        ctx.saved = None
+        if target._version != version:
+            raise RuntimeError('a tensor saved for the regression-loss backward was modified in place')
+        up = g.contiguous().float().reshape(1)
+        d = ops.reg_loss_bwd(diff, out, up, ctx.kind, *h.geom(), torch.empty_like(h.logits), h.ld)
+        h.d_logits = d if h.d_logits is None else h.d_logits.add_(d)     # several losses on one prediction: their gradients add
+        return up.new_empty(1), None, None, None, None
+
+
 class SoftCEFn(torch.autograd.Function):
     """SoftTargetCrossEntropy (dense f32 target [B, K]) or LabelSmoothingCrossEntropy (int64 labels [B] + smoothing) of the classification
     head's logits [B, K], f32 or bf16 (csrc/clsrecipe.hip): forward and backward are one launch each, the gradient comes back in the

@@ -5,6 +5,10 @@ and label map to the host, pickles them across ranks and runs numpy histograms, 
 keeps the four histograms of ``intersect_and_union`` (utils/semseg_metrics.py:49-59) in one int64 [4, K] device buffer, exchanges
 them with one all-reduce and evaluates the ratios of ``eval_metrics`` (:216-222).  np.histogram's closed last bin (a value equal
 to K counted into class K - 1) is not reproduced: predictions and labels outside [0, K) are dropped.
+
+Depth evaluation (``masked_nyu_metrics``, run_finetuning_depth.py:86-117, about thirty small launches and -- through
+``MetricLogger.update`` -- one ``.item()`` per metric and step): ``depth_metrics`` computes the seven values in one pass over the head's
+low-resolution map, ``DepthMetric`` keeps MetricLogger's running means on the device and reads them back once.
 """
 from __future__ import annotations
 
@@ -12,7 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .criterion import _seg_handle
+from .criterion import _refuse_under_capture, _seg_handle
 
 
 def seg_argmax(pred: torch.Tensor, num_classes: int) -> torch.Tensor:
@@ -60,6 +64,112 @@ class SegMetric:
 
     def compute(self):
         return ratios(self.hist.cpu().numpy())
+
+
+# ------------------------------------------------------------------------------------------
+# NYU depth metrics (run_finetuning_depth.py:86-117)
+# ------------------------------------------------------------------------------------------
+NYU_MEAN, NYU_STD = 2070.7764, 777.5723          # utils/data_constants.py:29-30
+DEPTH_METRIC_KEYS = ('rmse', 'rel', 'srel', 'log10', 'delta_1', 'delta_2', 'delta_3')
+
+
+def _depth_fused_ok(h, pred, target, mask_valid) -> bool:
+    if h is None or h.K != 1 or not torch.is_tensor(target):
+        return False
+    dev = h.logits.device
+    if target.dtype != torch.float32 or tuple(target.shape) != tuple(pred.shape) or target.device != dev:
+        return False
+    return mask_valid is None or (torch.is_tensor(mask_valid) and mask_valid.dtype == torch.bool and mask_valid.device == dev
+                                  and tuple(mask_valid.shape) == tuple(pred.shape))
+
+
+def _depth_metrics_eager(pred, target, mask_valid, mean, std) -> torch.Tensor:
+    """the seven values on the image itself as one f32 [7] tensor: sums over torch.where instead of boolean indexing, so nothing is
+    read back to the host"""
+    p, t = pred * std + mean, target * std + mean
+    if mask_valid is None:
+        valid = torch.ones_like(p, dtype=torch.bool)
+    else:
+        valid = mask_valid.bool() if mask_valid.shape[1] == p.shape[1] else mask_valid.bool().repeat_interleave(p.shape[1], 1)
+    n = valid.sum()
+    tc, pc = t.clamp_min(1e-6), p.clamp_min(1e-6)
+    over = lambda v: torch.where(valid, v, torch.zeros((), dtype=v.dtype, device=v.device)).sum() / n
+    d = (p - t).abs()
+    r = torch.maximum(p / tc, t / pc)
+    lg = pc.log() - tc.log()
+    return torch.stack([over(d * d).sqrt(), over(d / tc), over(d * d / tc), over(lg * lg).sqrt()]
+                       + [over((r < th).to(p.dtype)) for th in (1.25, 1.25 ** 2, 1.25 ** 3)])
+
+
+@torch.no_grad()
+def _depth_values(pred, target, mask_valid, mean, std, acc=None) -> torch.Tensor:
+    _refuse_under_capture(pred, 'depth_metrics')
+    h = _seg_handle(pred)
+    if _depth_fused_ok(h, pred, target, mask_valid):
+        mask = None if mask_valid is None else mask_valid.contiguous()
+        return ops.depth_metrics(h.logits, h.ld, target.contiguous(), mask, mean, std, h.B, h.h, h.w, h.H, h.W, h.mode, acc=acc)
+    out = _depth_metrics_eager(pred, target, mask_valid, mean, std).float()
+    if acc is not None:
+        acc[:7] += out
+        acc[7] += 1
+    return out
+
+
+def depth_metrics(pred: torch.Tensor, target: torch.Tensor, mask_valid=None, mean: float = NYU_MEAN, std: float = NYU_STD):
+    """``masked_nyu_metrics(preds, target, mask_valid)``: rmse, rel, srel, log10 (the natural logarithm, as the reference's key),
+    delta_1, delta_2, delta_3 of pred std + mean against target std + mean over the valid pixels, as a dict of 0-dim device tensors;
+    nothing is read back.  On an unmodified one-channel prediction of the ConvNeXt head with an f32 target and a torch.bool mask of
+    its shape the values come from one pass over the head's low-resolution map (csrc/regloss.hip) and the image is not written.
+    A head prediction inside a graph capture raises RuntimeError (criterion._refuse_under_capture)."""
+    out = _depth_values(pred, target, mask_valid, mean, std)
+    return {k: out[i] for i, k in enumerate(DEPTH_METRIC_KEYS)}
+
+
+class DepthMetric:
+    """What ``MetricLogger`` keeps for the depth loop, on the device: the mean over the update() calls of each per-batch metric
+    (``global_avg = total / count`` -- not a sum pooled over pixels) and of any extra 0-dim device tensor such as the loss.
+
+    update(pred, target, mask_valid, **scalars)   adds the batch's seven values and the scalars to the totals; no read-back
+    sync()                                        one all_reduce of totals and count when torch.distributed is initialised
+    compute()                                     {name: total / count} as Python floats -- the only read-back"""
+
+    def __init__(self, device=None, mean: float = NYU_MEAN, std: float = NYU_STD):
+        self.mean, self.std = float(mean), float(std)
+        self.names = list(DEPTH_METRIC_KEYS)
+        self.acc = None if device is None else torch.zeros((8,), device=device, dtype=torch.float32)      # seven totals, count
+        self.extra = None                                                                                 # the scalars' totals
+
+    def reset(self) -> None:
+        if self.acc is not None:
+            self.acc.zero_()
+        self.extra, self.names = None, list(DEPTH_METRIC_KEYS)
+
+    @torch.no_grad()
+    def update(self, pred: torch.Tensor, target: torch.Tensor, mask_valid=None, **scalars) -> None:
+        if self.acc is None:
+            self.acc = torch.zeros((8,), device=target.device, dtype=torch.float32)
+        if self.extra is None:
+            self.names = list(DEPTH_METRIC_KEYS) + list(scalars)
+            self.extra = torch.zeros((len(scalars),), device=self.acc.device, dtype=torch.float32)
+        if list(scalars) != self.names[7:]:
+            raise ValueError(f'DepthMetric.update: scalars {list(scalars)} differ from the first call\'s {self.names[7:]}')
+        _depth_values(pred, target, mask_valid, self.mean, self.std, acc=self.acc)
+        if scalars:
+            self.extra += torch.stack([v.detach().float().reshape(()) for v in scalars.values()])
+
+    def sync(self) -> None:
+        if self.acc is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            buf = self.acc if self.extra is None or not self.extra.numel() else torch.cat([self.acc, self.extra])
+            torch.distributed.all_reduce(buf)
+            if buf is not self.acc:
+                self.acc.copy_(buf[:8])
+                self.extra.copy_(buf[8:])
+
+    def compute(self):
+        tot = self.acc if self.extra is None else torch.cat([self.acc, self.extra])
+        v = tot.double().cpu()
+        vals = torch.cat([v[:7], v[8:]]) / v[7]
+        return {k: float(x) for k, x in zip(self.names, vals)}
 
 
 def ratios(hist: np.ndarray):

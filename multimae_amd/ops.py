@@ -1592,6 +1592,57 @@ def seg_hist(pred: Tensor, label: Tensor, K: int, ignore_index: int, hist: Tenso
     return hist
 
 
+# ------------------------------------------------- regression losses and depth metrics on the low-resolution map (csrc/regloss.hip) --
+REG_PARTIALS = 2048          # MMAE_REG_PARTIALS: rows of the per-workgroup partials scratch
+REG_MAX_K = 16               # MMAE_REG_MAX_K: channels the regression kernels take
+REG_KINDS = {'l1': 0, 'mse': 1, 'berhu': 2}
+
+
+def _mask_arg(mask: Optional[Tensor], B: int, K: int, H: int, W: int):
+    """(pointer, channels) of a torch.bool mask [B, 1 or K, H, W], contiguous; (None, 1) without one"""
+    if mask is None:
+        return None, 1
+    assert mask.dtype == torch.bool and mask.is_contiguous() and mask.dim() == 4 and mask.shape[1] in (1, K) \
+        and (mask.shape[0], mask.shape[2], mask.shape[3]) == (B, H, W), 'mask: contiguous torch.bool [B, 1 or K, H, W]'
+    return mask.data_ptr(), int(mask.shape[1])
+
+
+def reg_loss_fwd(x: Tensor, ldx: int, target: Tensor, mask: Optional[Tensor], kind: str, B: int, h: int, w: int, K: int, H: int, W: int,
+                 mode: str, diff: Optional[Tensor] = None):
+    """masked L1 / MSE / berHu of the interpolated prediction without the image: x f32 [B, h, w, ldx], target f32 [B, K, H, W], mask
+    torch.bool [B, 1 or K, H, W] or None -> (diff f32 [B, K, H, W] = prediction - target, 0 where masked,
+    out f32 [4] = (loss, valid count, max |diff|, berHu's c)); nothing is read back to the host."""
+    if diff is None:
+        diff = torch.empty((B, K, H, W), device=x.device, dtype=torch.float32)
+    mp, cm = _mask_arg(mask, B, K, H, W)
+    partial = torch.empty((4 * REG_PARTIALS,), device=x.device, dtype=torch.float32)
+    out = torch.empty((4,), device=x.device, dtype=torch.float32)
+    check(_lib.load().mmae_reg_loss_fwd(x.data_ptr(), ldx, target.data_ptr(), mp, cm, REG_KINDS[kind], B, h, w, K, H, W, RESIZE_MODES[mode],
+                                        diff.data_ptr(), partial.data_ptr(), out.data_ptr(), _stream()), 'reg_loss_fwd')
+    return diff, out
+
+
+def reg_loss_bwd(diff: Tensor, out: Tensor, up: Tensor, kind: str, B: int, h: int, w: int, K: int, H: int, W: int, mode: str, dx: Tensor,
+                 ldx: int) -> Tensor:
+    """its gradient: dx f32 [B, h, w, ldx] = up / count * d(sum)/dx (columns K .. ldx - 1 zeroed); up f32 [1] on the device"""
+    check(_lib.load().mmae_reg_loss_bwd(diff.data_ptr(), out.data_ptr(), up.data_ptr(), REG_KINDS[kind], B, h, w, K, H, W, RESIZE_MODES[mode],
+                                        dx.data_ptr(), ldx, _stream()), 'reg_loss_bwd')
+    return dx
+
+
+def depth_metrics(x: Tensor, ldx: int, target: Tensor, mask: Optional[Tensor], mean: float, std: float, B: int, h: int, w: int, H: int,
+                  W: int, mode: str, acc: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """the seven NYU depth metrics of the interpolated one-channel prediction: out f32 [7] = rmse, rel, srel, log10, delta_1..3; acc f32
+    [8] (optional): the seven values are added to acc[:7] and acc[7] += 1 on the device"""
+    mp, _ = _mask_arg(mask, B, 1, H, W)
+    partial = torch.empty((8 * REG_PARTIALS,), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((7,), device=x.device, dtype=torch.float32)
+    check(_lib.load().mmae_depth_metrics(x.data_ptr(), ldx, target.data_ptr(), mp, float(mean), float(std), B, h, w, H, W, RESIZE_MODES[mode],
+                                         partial.data_ptr(), out.data_ptr(), _p(acc), _stream()), 'depth_metrics')
+    return out
+
+
 # ------------------------------------------------- classification fine-tuning recipe (csrc/clsrecipe.hip) --------------------------
 MIX_ROW_WORDS = 8            # MMAE_MIX_ROW_WORDS: w_self, w_other, t_self, t_other (f32), yl, yh, xl, xh (i32) per sample
 MIX_BLEND, MIX_KEEP = -1, -2  # MMAE_MIX_BLEND / MMAE_MIX_KEEP in the yl word: blend without a box / sample not written
