@@ -663,10 +663,12 @@ typedef struct mmae_patch_src {
                                     (nn.Embedding raises a device assert there); 0 = unchecked */
 } mmae_patch_src;
 
+/* rows_dtype MMAE_BF16 / MMAE_F32; any other code (MMAE_F16 included) is refused with MMAE_ESUPPORT before anything is written. */
 int mmae_patch_rows(const mmae_patch_src* srcs_host, const int32_t* task_offsets_host, int T, const int64_t* sel,
                     void* rows, int rows_dtype, int B, int n_sel, int Ktot, void* stream);
 /* d_emb[cls][e] += d_rows[row][k_off + e*ph*pw + i*pw + j] over the selected tokens in
- * [tok_off, tok_off + n_patches); d_rows act dtype [B*n_sel][ld].  (float atomics) */
+ * [tok_off, tok_off + n_patches); d_rows [B*n_sel][ld], rows_dtype MMAE_BF16 / MMAE_F32 (any other code, MMAE_F16 included, is
+ * refused with MMAE_ESUPPORT before anything is written).  (float atomics) */
 int mmae_semseg_emb_bwd(const void* d_rows, int rows_dtype, int64_t ld, const int64_t* cls, const int64_t* sel, float* d_emb,
                         int B, int H, int W, int E, int ph, int pw, int n_sel, int k_off, int tok_off, int n_patches, int n_cls,
                         void* stream);
@@ -746,7 +748,8 @@ int mmae_decoder_build_bwd(const float* d_queries, const float* d_context, const
  * b c (nh ph) (nw pw)', output_adapters.py:277-280, and its transpose for autograd.
  * ------------------------------------------------------------------------- */
 int mmae_unpatchify(const float* patches, float* img, int B, int C, int nh, int nw, int ph, int pw, void* stream);
-/* patches act dtype [B*nh*nw][ld], ld >= C*ph*pw (columns beyond C*ph*pw are left untouched) */
+/* patches [B*nh*nw][ld], ld >= C*ph*pw (columns beyond C*ph*pw are left untouched); patches_dtype MMAE_BF16 / MMAE_F32 (any other
+ * code, MMAE_F16 included, is refused with MMAE_ESUPPORT before anything is written) */
 int mmae_patchify(const float* img, void* patches, int patches_dtype, int64_t ld, int B, int C, int nh, int nw, int ph,
                   int pw, void* stream);
 

@@ -676,6 +676,7 @@ int mmae_patch_rows(const mmae_patch_src* srcs, const int32_t* task_offsets_host
     MMAE_REQUIRE(srcs && task_offsets_host && sel && rows && B > 0 && n_sel > 0 && Ktot > 0, "patch_rows: bad argument");
     TaskTable tt;
     MMAE_REQUIRE(fill_tt(tt, task_offsets_host, T) == 0, "patch_rows: 1 <= T <= 8");
+    if (rows_dtype != MMAE_BF16 && rows_dtype != MMAE_F32) { mmae_set_error("patch_rows: bf16 / f32 rows"); return MMAE_ESUPPORT; }
     PatchSrcs ps;
     for (int t = 0; t < MAX_TASKS; ++t) {
         const mmae_patch_src& s = srcs[t < T ? t : 0];
@@ -696,6 +697,7 @@ int mmae_semseg_emb_bwd(const void* d_rows, int rows_dtype, int64_t ld, const in
                         void* stream) {
     MMAE_REQUIRE(d_rows && cls && sel && d_emb && B > 0 && n_cls > 0 && E > 0, "semseg_emb_bwd: bad argument");
     MMAE_REQUIRE((size_t)n_cls * E * 4 <= 160 * 1024, "semseg_emb_bwd: embedding table exceeds LDS");
+    if (rows_dtype != MMAE_BF16 && rows_dtype != MMAE_F32) { mmae_set_error("semseg_emb_bwd: bf16 / f32 rows"); return MMAE_ESUPPORT; }
     const long long n_rows = (long long)B * n_sel;
     const int grid = (int)(n_rows < 512 ? n_rows : 512);
     const size_t lds = (size_t)n_cls * E * 4;
@@ -874,6 +876,7 @@ int mmae_unpatchify(const float* patches, float* img, int B, int C, int nh, int 
 
 int mmae_patchify(const float* img, void* patches, int patches_dtype, int64_t ld, int B, int C, int nh, int nw, int ph, int pw, void* stream) {
     MMAE_REQUIRE(patches && img && B > 0 && C > 0 && ld >= (int64_t)C * ph * pw, "patchify: bad argument");
+    if (patches_dtype != MMAE_BF16 && patches_dtype != MMAE_F32) { mmae_set_error("patchify: bf16 / f32 patches"); return MMAE_ESUPPORT; }
     const long long total = (long long)B * C * nh * ph * nw * pw;
     hipStream_t st = (hipStream_t)stream;
     const int cbp = (pw % 4 == 0 && pw < 16 && ld % 4 == 0) ? patch_tile_cb(ph, nw * pw) : 0;

@@ -1277,11 +1277,14 @@ def patch_embed_fwd(srcs: Sequence[dict], weights_bf16: Sequence[Tensor], biases
 
 def semseg_emb_bwd(d_rows: Tensor, cls: Tensor, sel: Tensor, d_emb: Tensor, *, B, H, W, E, ph, pw, n_sel, k_off, tok_off,
                    n_patches, n_cls, accumulate: bool = True, deterministic: bool = True) -> None:
-    """Gradient of the class-embedding table.  deterministic (default, round 6): fixed summation order, no atomics (mmae_semseg_emb_bwd_det) for
-    bf16 / f32 rows whose table fits the LDS; accumulate=False stores the gradient, so d_emb needs no zero-fill.  Otherwise (fp16 rows, huge tables)
-    the float-atomic form, which ADDS into d_emb (accumulate=False then zero-fills it first)."""
+    """Gradient of the class-embedding table.  d_rows bf16 or f32 -- the two flavours the kernels have; any other dtype (fp16 included) raises.
+    deterministic (default, round 6): fixed summation order, no atomics (mmae_semseg_emb_bwd_det) when the table fits the LDS; accumulate=False
+    stores the gradient, so d_emb needs no zero-fill.  Otherwise (huge tables, deterministic=False) the float-atomic form, which ADDS into d_emb
+    (accumulate=False then zero-fills it first)."""
+    if d_rows.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f'semseg_emb_bwd: d_rows must be bf16 or f32, not {d_rows.dtype}')
     lib = _lib.load()
-    ws_elems = int(lib.mmae_semseg_emb_bwd_ws_elems(B, n_sel, E, n_cls)) if (deterministic and d_rows.dtype in (torch.bfloat16, torch.float32)) else -1
+    ws_elems = int(lib.mmae_semseg_emb_bwd_ws_elems(B, n_sel, E, n_cls)) if deterministic else -1
     if ws_elems > 0:
         ws = torch.empty(ws_elems, device=d_rows.device, dtype=torch.float32)
         check(lib.mmae_semseg_emb_bwd_det(d_rows.data_ptr(), dcode(d_rows.dtype), d_rows.stride(0), cls.data_ptr(), sel.data_ptr(), d_emb.data_ptr(),

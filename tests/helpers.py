@@ -164,23 +164,25 @@ def assert_within(out, ref, bound, what: str, names=None):
 
 # ----------------------------------------------------------------------------------------------
 # Guarded outputs and poisoned operands
-_INT_OF = {1: torch.uint8, 2: torch.int16, 4: torch.int32}
-# the sentinel: bytes a5 ff repeated -- a NaN as bf16 / fp16 (0xffa5) and as f32 (0xffa5ffa5)
-_SENT = {2: -91, 4: -5898331}                      # int16 0xffa5, int32 0xffa5ffa5
+_INT_OF = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+# the sentinel: bytes a5 ff repeated -- a NaN as bf16 / fp16 (0xffa5) and as f32 (0xffa5ffa5); as an int64 output (8-byte elements: the
+# mask sampler's ids) a large negative number no index or mask value can equal
+_SENT = {2: -91, 4: -5898331, 8: 0xffa5ffa5ffa5ffa5 - 2 ** 64}      # int16 0xffa5, int32 0xffa5ffa5, int64 0xffa5ffa5ffa5ffa5
 
 
 class Guarded:
     """One flat allocation that holds the logical [rows][cols] view with leading dimension ld >= cols, `guard` elements of
     guard zone before it and after it.  Every element outside the view holds a fixed sentinel bit pattern (a NaN in every
     float format here); intact() asserts that all of them still do, bit for bit.  Pass `flat` with element offset `off` (or
-    `full` / `view`, which start at the view) to the code under test."""
+    `full` / `view`, which start at the view) to the code under test.  `shift` elements are left unused in front of it all: the
+    allocator's alignment (and guard % 8 == 0) puts the view on a 16-byte boundary, a shift takes it off again."""
 
-    def __init__(self, rows: int, cols: int, ld: int, dtype, device, guard: int = 64, fill=None):
+    def __init__(self, rows: int, cols: int, ld: int, dtype, device, guard: int = 64, fill=None, shift: int = 0):
         assert ld >= cols and guard % 8 == 0 and ld > 0
         self.rows, self.cols, self.ld, self.dtype, self.off = rows, cols, ld, dtype, guard
         self.esz = torch.empty((), dtype=dtype).element_size()
         n = guard + rows * ld + guard
-        self.flat = torch.empty((n,), dtype=dtype, device=device)
+        self.flat = torch.empty((n + shift,), dtype=dtype, device=device)[shift:]
         self._bits().fill_(_SENT[self.esz])
         self.full = self.flat[guard:guard + rows * ld].view(rows, ld)
         self.view = self.full[:, :cols]
@@ -646,3 +648,126 @@ def x3_split_ref(x):
     x = x.detach().cpu().float()
     hi = bf16_bits_ref(x)
     return hi, bf16_bits_ref(x - bf16_to_f32_ref(hi))
+
+
+# ----------------------------------------------------------------------------------------------
+# The input side (tokens.hip: patch_rows, semseg_emb_bwd[_det], mask_sample; embed.hip: patch_embed_fwd), from mmae.h's formulae.  A
+# task is a dict: data (f32 [B][C][H][W], kind 0; int64 class ids [B][H][W], kind 1), emb (f32 [n_cls][C], kind 1), kind, C, H, W, ph,
+# pw, k_off, n_cls.  Token idx of task t (offs[t] <= idx < offs[t + 1]) is patch p = idx - offs[t] at (p // (W / pw), p % (W / pw)).
+def _task_patches(s):
+    """every patch of one task flattened in (c, i, j) order: f32 [B][(H / ph) (W / pw)][C ph pw], copies only (NaN payloads survive);
+    class ids outside [0, n_cls) embed as zeros"""
+    d = s['data']
+    C, H, W, ph, pw = s['C'], s['H'], s['W'], s['ph'], s['pw']
+    if s['kind'] == 1:
+        ok = (d >= 0) & (d < s['n_cls'])
+        e = s['emb'].float()[torch.where(ok, d, torch.zeros_like(d))]                     # [B][H][W][C]
+        d = torch.where(ok[..., None], e, torch.zeros_like(e)).permute(0, 3, 1, 2)
+    B = d.shape[0]
+    return d.reshape(B, C, H // ph, ph, W // pw, pw).permute(0, 2, 4, 1, 3, 5).reshape(B, (H // ph) * (W // pw), C * ph * pw)
+
+
+def token_owner(idx, offs):
+    """task of every token index: the last t with offs[t] <= idx (an empty task owns nothing)"""
+    return torch.bucketize(idx, torch.as_tensor(list(offs[1:-1]), dtype=idx.dtype, device=idx.device), right=True)
+
+
+def patch_rows_ref(srcs, offs, sel, Ktot: int):
+    """mmae_patch_rows in f32 [B * n_sel][Ktot]: row (b, r) holds the flattened patch of token sel[b][r] at its task's k_off, zeros in
+    every other column -- gaps between segments and a tail past the last one included.  The bf16 form is bf16_bits_ref of it."""
+    B, n_sel = sel.shape
+    out = torch.zeros(B * n_sel, Ktot, dtype=torch.float32)
+    flat = sel.reshape(-1)
+    own = token_owner(flat, offs)
+    bidx = torch.arange(B).repeat_interleave(n_sel)
+    for t, s in enumerate(srcs):
+        m = own == t
+        K = s['C'] * s['ph'] * s['pw']
+        assert s['k_off'] >= 0 and s['k_off'] + K <= Ktot
+        out[m, s['k_off']:s['k_off'] + K] = _task_patches(s)[bidx[m], flat[m] - offs[t]]
+    return out
+
+
+def patch_embed_ref(srcs, ws, bs, poss, offs, sel, glob, D: int):
+    """mmae_patch_embed_fwd in fp64 on the operands as the kernel multiplies them -- the patch and the weight rounded to bf16, bias and
+    position row in f32: tok[b][r] = W_t . x^ + b_t + pos_t[p], tok[b][n_sel + g] = glob[g] (a copy: bound 0).  Bound of a token
+    element: K_t exact products summed in fp32 in any order, then the two fp32 additions of the epilogue,
+        gamma(K_t + 2) (|W_t| . |x^| + |b_t| + |pos_t[p]|) + ulp_f32(|ref| + that)
+    Returns (tok fp64 [B][n_sel + G][D], bound, x^ as f32 [B * n_sel][sum K_t as laid out by k_off] -- None of it read from the GPU)."""
+    B, n_sel = sel.shape
+    G = 0 if glob is None else glob.shape[0]
+    Kend = max(s['k_off'] + s['C'] * s['ph'] * s['pw'] for s in srcs)
+    xh = bf16_to_f32_ref(bf16_bits_ref(patch_rows_ref(srcs, offs, sel, Kend)))
+    ref = torch.zeros(B, n_sel + G, D, dtype=torch.float64)
+    bound = torch.zeros_like(ref)
+    flat = sel.reshape(-1)
+    own = token_owner(flat, offs)
+    r2, b2 = torch.zeros(B * n_sel, D, dtype=torch.float64), torch.zeros(B * n_sel, D, dtype=torch.float64)
+    for t, s in enumerate(srcs):
+        m = own == t
+        if not bool(m.any()):
+            continue
+        K = s['C'] * s['ph'] * s['pw']
+        X = xh[m, s['k_off']:s['k_off'] + K].double()
+        Wt = bf16_to_f32_ref(bf16_bits_ref(ws[t].float().reshape(D, K))).double()
+        add = bs[t].double()[None, :] + poss[t].double()[flat[m] - offs[t]]
+        absadd = bs[t].double().abs()[None, :] + poss[t].double().abs()[flat[m] - offs[t]]
+        rt = X @ Wt.t() + add
+        r2[m] = rt
+        b2[m] = prod_bound(X.abs(), Wt.abs(), K + 2, torch.float32, rt, extra=gamma(K + 2) * absadd)
+    ref[:, :n_sel] = r2.view(B, n_sel, D)
+    bound[:, :n_sel] = b2.view(B, n_sel, D)
+    if G:
+        ref[:, n_sel:] = glob.double()
+    return ref, bound, xh
+
+
+def semseg_emb_grad_ref(d_rows, cls, sel, *, E, ph, pw, k_off, tok_off, n_patches, n_cls):
+    """Gradient of the class-embedding table (mmae_semseg_emb_bwd[_det]) in fp64: d_emb[c][e] = sum over the selected tokens of
+    [tok_off, tok_off + n_patches) and their pixels (i, j) with class c of d_rows[row][k_off + e ph pw + i pw + j]; ids outside
+    [0, n_cls) contribute nothing.  d_rows [B * n_sel][ld] (any float type), cls int64 [B][H][W], sel [B][n_sel].
+    Returns (grad [n_cls][E], n [n_cls][1] the number of terms of each entry, S [n_cls][E] = sum |term|)."""
+    B, H, W = cls.shape
+    n_sel = sel.shape[1]
+    nh, nw = H // ph, W // pw
+    assert nh * nw == n_patches
+    p = sel.reshape(-1).cpu() - tok_off
+    rows = torch.nonzero((p >= 0) & (p < n_patches)).reshape(-1)
+    b = rows // n_sel
+    ids = cls.cpu().reshape(B, nh, ph, nw, pw).permute(0, 1, 3, 2, 4).reshape(B, nh * nw, ph * pw)[b, p[rows]]          # [R][ph pw]
+    terms = d_rows.detach().cpu()[rows, k_off:k_off + E * ph * pw].double().reshape(-1, E, ph * pw).permute(0, 2, 1)    # [R][ph pw][E]
+    ids, terms = ids.reshape(-1), terms.reshape(-1, E)
+    ok = (ids >= 0) & (ids < n_cls)
+    grad = torch.zeros(n_cls, E, dtype=torch.float64)
+    S = torch.zeros_like(grad)
+    grad.index_add_(0, ids[ok], terms[ok])
+    S.index_add_(0, ids[ok], terms[ok].abs())
+    n = torch.bincount(ids[ok], minlength=n_cls).double()[:, None]
+    return grad, n, S
+
+
+def semseg_emb_grad_bound(grad, n, S):
+    """any summation tree of the n fp32 terms of an entry is within gamma(n) S (so neither the sub-tables nor the grid matter), one more
+    addition for `accumulate`: gamma(n + 1) S, + the final ulp as prod_bound adds it.  An entry without terms: exactly 0."""
+    nn = n + 1
+    b = nn * U32 / (1.0 - nn * U32) * S
+    return torch.where(n > 0, b + ulp(torch.float32, grad.abs() + b), torch.zeros_like(b))
+
+
+def mask_sample_ref(spt, task_noise, all_noise, offs, n_keep: int):
+    """mmae_mask_sample restated with stable argsorts (mmae.h; multimae.py:191-216): per task, order = the stable argsort of its noise;
+    SORTED POSITION j is pre-selected iff order[j] < k_t (the reference's quirk: the position, not the token of that rank); the keys
+    (0 pre-selected / 1 not) + all_noise, one f32 addition, are sorted stably again: ids_restore[b][j] = rank of token j, the first
+    n_keep ranks are visible (mask 0) and ids_keep lists them by rank.  spt int64 [B][T], task_noise / all_noise f32 [B][Ntot].
+    Returns int64 (mask_all, ids_keep, ids_restore)."""
+    B, Ntot = all_noise.shape
+    key = torch.empty(B, Ntot, dtype=torch.float32)
+    for t in range(len(offs) - 1):
+        lo, hi = offs[t], offs[t + 1]
+        order = torch.argsort(task_noise[:, lo:hi].float(), dim=1, stable=True)
+        key[:, lo:hi] = (order >= spt[:, t:t + 1]).float()
+    key = key + all_noise.float()
+    shuffle = torch.argsort(key, dim=1, stable=True)
+    restore = torch.empty_like(shuffle)
+    restore.scatter_(1, shuffle, torch.arange(Ntot).expand(B, Ntot).contiguous())
+    return (restore >= n_keep).long(), shuffle[:, :n_keep].contiguous(), restore

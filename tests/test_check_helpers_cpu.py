@@ -459,3 +459,206 @@ def test_ops_refuses_a_shadow_dtype_the_optimiser_kernels_do_not_write():
     for dt in (torch.float16, torch.float64, torch.int16):
         with pytest.raises(TypeError, match='float32 or bfloat16'):
             ops._shadow_args(torch.zeros(8, dtype=dt))
+
+
+# ---- the input side: patch rows, fused patch embedding, class-embedding gradient, mask sampler ---------------------------------
+from helpers import (mask_sample_ref, patch_embed_ref, patch_rows_ref, semseg_emb_grad_bound, semseg_emb_grad_ref,  # noqa: E402
+                     token_owner)
+
+
+def _input_case(B=128, seed=21):
+    """two tasks, neither image nor patch square, both with K = 96: class ids 8 x 12 in 2 x 4 patches (E = 12, 7 classes, ids drawn from
+    [-1, 7]) at k_off 104, an image 3 x 16 x 24 in 4 x 8 patches at k_off 0; columns 96 .. 104 are a gap, 200 .. 208 a tail.  Every
+    token of both tasks is selected, in a random order per sample."""
+    g_ = torch.Generator().manual_seed(seed)
+    srcs = [dict(data=torch.randint(-1, 8, (B, 8, 12), generator=g_), emb=torch.randn(7, 12, generator=g_), kind=1, C=12, H=8, W=12,
+                 ph=2, pw=4, k_off=104, n_cls=7),
+            dict(data=torch.randn(B, 3, 16, 24, generator=g_), emb=None, kind=0, C=3, H=16, W=24, ph=4, pw=8, k_off=0, n_cls=0)]
+    offs = [0, 12, 24]
+    sel = torch.stack([torch.randperm(24, generator=g_) for _ in range(B)])
+    return srcs, offs, sel, 208, g_
+
+
+def _rows_by_index(srcs, offs, sel, Ktot, swap_patch=False, swap_grid=False):
+    """patch_rows_kernel's index arithmetic, column by column: (c, i, j) of column k, pixel (py ph + i, px pw + j) of patch p =
+    (py, px).  swap_patch decodes (i, j) with ph in pw's place, swap_grid decodes (py, px) with H / ph in W / pw's place (both kept
+    inside the image by a modulo, so the wrong kernel reads a wrong pixel, not past the end)."""
+    B, n_sel = sel.shape
+    out = torch.zeros(B * n_sel, Ktot)
+    flat = sel.reshape(-1)
+    own = token_owner(flat, offs)
+    b = torch.arange(B).repeat_interleave(n_sel)
+    for t, s in enumerate(srcs):
+        m = own == t
+        C, H, W, ph, pw = s['C'], s['H'], s['W'], s['ph'], s['pw']
+        p = flat[m] - offs[t]
+        nw = H // ph if swap_grid else W // pw
+        py, px = (p // nw)[:, None], (p % nw)[:, None]
+        kk = torch.arange(C * ph * pw)[None, :]
+        c, ij = kk // (ph * pw), kk % (ph * pw)
+        q = ph if swap_patch else pw
+        y, x = (py * ph + ij // q) % H, (px * pw + ij % q) % W
+        bb = b[m][:, None]
+        if s['kind'] == 0:
+            v = s['data'][bb, c, y, x]
+        else:
+            ids = s['data'][bb, y, x]
+            ok = (ids >= 0) & (ids < s['n_cls'])
+            v = torch.where(ok, s['emb'][ids.clamp(0, s['n_cls'] - 1), c], torch.zeros(()))
+        out[m, s['k_off']:s['k_off'] + C * ph * pw] = v
+    return out
+
+
+def test_patch_rows_ref_equals_the_index_arithmetic_and_flags_the_swaps():
+    srcs, offs, sel, Ktot, _ = _input_case(B=3)
+    ref = patch_rows_ref(srcs, offs, sel, Ktot)
+    assert torch.equal(ref, _rows_by_index(srcs, offs, sel, Ktot))
+    assert bool((ref[:, 96:104] == 0).all()) and bool((ref[:, 200:] == 0).all())            # the gap and the tail
+    own = token_owner(sel.reshape(-1), offs)
+    assert bool((ref[own == 0, :96] == 0).all()) and bool((ref[own == 1, 104:] == 0).all())    # the other task's segment
+    assert not torch.equal(ref, _rows_by_index(srcs, offs, sel, Ktot, swap_patch=True))
+    assert not torch.equal(ref, _rows_by_index(srcs, offs, sel, Ktot, swap_grid=True))
+    bad = ref.clone()
+    bad[5, 64:96] = 0                                        # the last 32 of a segment's 96 columns
+    assert not torch.equal(ref, bad)
+    srcs[1]['data'][1, 2, 5, 9] = float('nan')               # a copy: NaNs and their payloads come through
+    r2 = patch_rows_ref(srcs, offs, sel, Ktot)
+    assert int(torch.isnan(r2).sum()) == 1 and torch.equal(r2.view(torch.int32), _rows_by_index(srcs, offs, sel, Ktot).view(torch.int32))
+
+
+def _embed_operands(srcs, g_, D=32):
+    ws = [(torch.randn(D, 96, generator=g_) * 96 ** -0.5).bfloat16() for _ in srcs]
+    bs = [torch.randn(D, generator=g_) for _ in srcs]
+    poss = [torch.randn(12, D, generator=g_) for _ in srcs]
+    return ws, bs, poss, torch.randn(2, D, generator=g_)
+
+
+def _embed_f32(rows, srcs, ws, bs, poss, offs, sel, glob):
+    """the kernel's arithmetic in plain f32 on given patch rows: bf16 operands, f32 products and sums, (acc + bias) + pos"""
+    B, n_sel = sel.shape
+    D = glob.shape[1]
+    flat = sel.reshape(-1)
+    own = token_owner(flat, offs)
+    xh = rows.bfloat16().float()
+    tok = torch.zeros(B * n_sel, D)
+    for t, s in enumerate(srcs):
+        m = own == t
+        tok[m] = (xh[m, s['k_off']:s['k_off'] + 96] @ ws[t].float().t() + bs[t]) + poss[t][flat[m] - offs[t]]
+    return torch.cat([tok.view(B, n_sel, D), glob.expand(B, -1, -1)], 1)
+
+
+def test_patch_embed_ref_passes_a_plain_f32_restatement():
+    srcs, offs, sel, Ktot, g_ = _input_case()
+    ws, bs, poss, glob = _embed_operands(srcs, g_)
+    ref, bound, xh = patch_embed_ref(srcs, ws, bs, poss, offs, sel, glob, 32)
+    assert torch.equal(xh, patch_rows_ref(srcs, offs, sel, 200).bfloat16().float())
+    out = _embed_f32(_rows_by_index(srcs, offs, sel, Ktot), srcs, ws, bs, poss, offs, sel, glob)
+    assert_within(out, ref, bound, 'f32 patch embedding', names=('b', 'r', 'd'))
+    assert torch.equal(ref[:, 24:], glob.double().expand(128, -1, -1)) and float(bound[:, 24:].abs().max()) == 0.0
+    assert float(bound[:, :24].min()) > 0.0
+
+
+@pytest.mark.parametrize('corruption,old_passes', [('ph and pw swapped', False), ('H/ph and W/pw swapped', False),
+                                                   ('last K chunk of one row dropped', True)])
+def test_patch_embed_corruptions_are_flagged(corruption, old_passes):
+    """the old criterion: rel_err < 1e-2 over all token rows (test_patch_embed_assemble_vs_oracle's bf16 tolerance)"""
+    srcs, offs, sel, Ktot, g_ = _input_case()
+    ws, bs, poss, glob = _embed_operands(srcs, g_)
+    ref, bound, _ = patch_embed_ref(srcs, ws, bs, poss, offs, sel, glob, 32)
+    rows = _rows_by_index(srcs, offs, sel, Ktot, swap_patch=corruption == 'ph and pw swapped', swap_grid=corruption == 'H/ph and W/pw swapped')
+    if corruption == 'last K chunk of one row dropped':
+        r = 24 * 77 + 23
+        k0 = srcs[int(token_owner(sel.reshape(-1)[r:r + 1], offs))]['k_off']
+        rows[r, k0 + 64:k0 + 96] = 0                         # 32 of the 96 columns
+    bad = _embed_f32(rows, srcs, ws, bs, poss, offs, sel, glob)
+    assert (rel_err(bad, ref) < 1e-2) == old_passes
+    with pytest.raises(AssertionError, match='outside the bound'):
+        assert_within(bad, ref, bound, corruption, names=('b', 'r', 'd'))
+
+
+def _emb_grad_f32(d_rows, srcs, offs, sel, swap_patch=False, swap_grid=False, drop_row=None):
+    """the class-embedding gradient as a chain of f32 additions, pixel by pixel, with patch_rows_kernel's index arithmetic"""
+    s = srcs[0]
+    E, H, W, ph, pw = s['C'], s['H'], s['W'], s['ph'], s['pw']
+    B, n_sel = sel.shape
+    flat = sel.reshape(-1)
+    rows = torch.nonzero(token_owner(flat, offs) == 0).reshape(-1)
+    p = flat[rows] - offs[0]
+    nw = H // ph if swap_grid else W // pw
+    q = ph if swap_patch else pw
+    ij = torch.arange(ph * pw)[None, :]
+    y, x = ((p // nw)[:, None] * ph + ij // q) % H, ((p % nw)[:, None] * pw + ij % q) % W
+    ids = s['data'][(rows // n_sel)[:, None], y, x].reshape(-1)
+    d = d_rows.clone()
+    if drop_row is not None:
+        d[rows[drop_row], s['k_off'] + 64:s['k_off'] + 96] = 0
+    terms = d[rows, s['k_off']:s['k_off'] + E * ph * pw].reshape(-1, E, ph * pw).permute(0, 2, 1).reshape(-1, E)
+    ok = (ids >= 0) & (ids < s['n_cls'])
+    tab = torch.zeros(s['n_cls'], E)
+    for c in range(s['n_cls']):
+        tc = terms[ok & (ids == c)]
+        for i in range(tc.shape[0]):
+            tab[c] += tc[i]
+    return tab
+
+
+def _emb_grad_case():
+    srcs, offs, sel, Ktot, g_ = _input_case(B=4)
+    srcs[0]['data'][srcs[0]['data'] == 3] = 4                 # class 3 is never hit
+    d_rows = torch.randn(4 * 24, 216, generator=g_)           # ld 216 > Ktot
+    s = srcs[0]
+    kw = dict(E=s['C'], ph=s['ph'], pw=s['pw'], k_off=s['k_off'], tok_off=0, n_patches=12, n_cls=7)
+    return srcs, offs, sel, d_rows, kw
+
+
+def test_semseg_emb_grad_ref_passes_a_plain_f32_restatement():
+    srcs, offs, sel, d_rows, kw = _emb_grad_case()
+    grad, n, S = semseg_emb_grad_ref(d_rows, srcs[0]['data'], sel, **kw)
+    bound = semseg_emb_grad_bound(grad, n, S)
+    assert float(n.sum()) == float(((srcs[0]['data'] >= 0) & (srcs[0]['data'] < 7)).sum())      # every token is selected: every valid pixel is a term
+    assert float(n[3]) == 0 and float(grad[3].abs().max()) == 0.0 and float(bound[3].max()) == 0.0
+    assert_within(_emb_grad_f32(d_rows, srcs, offs, sel), grad, bound, 'f32 class-embedding gradient', names=('class', 'e'))
+
+
+@pytest.mark.parametrize('corruption', ['ph and pw swapped', 'H/ph and W/pw swapped', 'last K chunk of one row dropped'])
+def test_semseg_emb_grad_corruptions_are_flagged(corruption):
+    srcs, offs, sel, d_rows, kw = _emb_grad_case()
+    grad, n, S = semseg_emb_grad_ref(d_rows, srcs[0]['data'], sel, **kw)
+    bad = _emb_grad_f32(d_rows, srcs, offs, sel, swap_patch=corruption == 'ph and pw swapped', swap_grid=corruption == 'H/ph and W/pw swapped',
+                        drop_row=5 if corruption == 'last K chunk of one row dropped' else None)
+    with pytest.raises(AssertionError, match='outside the bound'):
+        assert_within(bad, grad, semseg_emb_grad_bound(grad, n, S), corruption, names=('class', 'e'))
+
+
+def test_mask_sample_ref_known_answer_and_the_oracle():
+    import multimae_oracle as orc
+    # the quirk: order = argsort(noise) = [1, 2, 0, 3]; POSITIONS 0 and 2 hold order < 2, so tokens 0 and 2 are pre-selected (not 1 and 2)
+    m, k, r = mask_sample_ref(torch.tensor([[2]]), torch.tensor([[0.3, 0.1, 0.2, 0.4]]), torch.tensor([[0.5, 0.6, 0.7, 0.8]]), [0, 4], 2)
+    assert m.tolist() == [[0, 1, 0, 1]] and k.tolist() == [[0, 2]] and r.tolist() == [[0, 2, 1, 3]]
+    g_ = torch.Generator().manual_seed(22)
+    for offs in ([0, 49, 113, 309], [0, 16, 16, 40], [0, 7]):
+        T, N, B = len(offs) - 1, offs[-1], 9
+        tn, an = torch.rand(B, N, generator=g_), torch.rand(B, N, generator=g_)
+        tn[1, 1:5] = tn[1, 0]                                 # ties in both arrays
+        an[2, 3:6] = an[2, 0]
+        spt = torch.stack([torch.tensor([int(torch.randint(0, offs[t + 1] - offs[t] + 1, (1,), generator=g_)) for t in range(T)]) for _ in range(B)])
+        for n_keep in (0, 1, N // 3, N):
+            mine = mask_sample_ref(spt, tn, an, offs, n_keep)
+            theirs = orc.masks_from_noise(spt, [tn[:, offs[t]:offs[t + 1]] for t in range(T)], an, n_keep)
+            assert all(torch.equal(a, b) for a, b in zip(mine, theirs)), (offs, n_keep)
+            assert mine[0].dtype == mine[1].dtype == mine[2].dtype == torch.int64
+            assert torch.equal(torch.sort(mine[2], 1).values, torch.arange(N).expand(B, -1)) and bool((mine[0] == 0).sum(1).eq(n_keep).all())
+
+
+def test_guarded_int64_buffer_flags_a_write_into_one_guard_element():
+    gb = Guarded(5, 7, 9, torch.int64, 'cpu')
+    gb.view.copy_(torch.arange(35).view(5, 7))
+    gb.intact()
+    assert int(gb.flat[0]) == 0xffa5ffa5ffa5ffa5 - 2 ** 64
+    gb.full[2, 8] = 0
+    with pytest.raises(AssertionError, match=r'row 2, col 8'):
+        gb.intact()
+    gb2 = Guarded(5, 7, 7, torch.int64, 'cpu')
+    gb2.flat[gb2.off - 1] = 3
+    with pytest.raises(AssertionError, match='guard zone before'):
+        gb2.intact()
