@@ -236,6 +236,31 @@ def depth_metric(device=None):
     return DepthMetric(device)
 
 
+def prepare_dense_inputs(input_dict: dict, tasks_dict: dict, standardize_depth: bool) -> dict:
+    """Replaces the two blocks between the ``input_dict`` comprehension and the forward pass of run_finetuning_depth.py (:671-695
+    in ``train_one_epoch``, :808-832 in ``evaluate``) and of run_finetuning_taskonomy.py (:645-668, :766-789), without a sort, a
+    Python loop over device scalars or a boolean temporary -- no host synchronisation:
+
+      - ``standardize_depth`` and ``'depth' in input_dict``: ``input_dict['depth']`` is REBOUND to
+        ``robust_depth_standardize(input_dict['depth'], tasks_dict['mask_valid'])``, a new tensor that is already 0 where the mask
+        is not set.  ``tasks_dict['depth']``, the loss target, was the same object and stays raw, as in the reference (:687).
+      - every other non-rgb input is masked IN PLACE with ``mask_invalid_``, as in the reference (:691-695) -- and, as there, an
+        input that was not standardised is the very tensor ``tasks_dict[task]`` holds, so the target of that task is masked with it.
+      - an rgb-only ``input_dict`` (every shipped cfgs/finetune/{depth,taskonomy} config) makes no library call and no launch.
+
+    Returns ``input_dict``."""
+    from multimae_amd import data_ops
+    done = None
+    if standardize_depth and 'depth' in input_dict:
+        input_dict['depth'] = data_ops.robust_depth_standardize(input_dict['depth'], tasks_dict['mask_valid'])
+        done = 'depth'
+    for task in input_dict:
+        if task in ('rgb', done):
+            continue
+        data_ops.mask_invalid_(input_dict[task], tasks_dict['mask_valid'])
+    return input_dict
+
+
 def mixup(args):
     """Replaces the ``Mixup(...)`` construction of run_finetuning_cls.py:299-306: the engine's ``multimae_amd.Mixup`` from the same
     arguments, or None when ``--mixup``, ``--cutmix`` and ``--cutmix_minmax`` are all off."""

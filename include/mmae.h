@@ -901,6 +901,32 @@ int mmae_opt_step_groups(const mmae_opt_groups_desc* d, void* stream);
 int mmae_depth_standardize(const float* x, float* y, int B, int n, int lo, int hi, float eps, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Mask-aware robust depth standardisation of the fine-tuning loops (run_finetuning_depth.py:671-688 and :808-825,
+ * run_finetuning_taskonomy.py:645-661 and :766-782: clone, NaN under the mask, torch.sort, a Python loop of device-scalar
+ * slices with a mean and a var per sample, a boolean-mask fill).  x, y f32 [B][n] (y may alias x); mask [B][n] bytes, the
+ * storage of a torch.bool tensor, non-zero = valid; NULL = all valid.  Per sample:
+ *   an element takes part iff its mask byte is non-zero and its value is not a NaN; n_valid is their count;
+ *   lo = (int)((float)n_valid * lo_frac), hi = (int)((float)n_valid * hi_frac): one f32 product each, truncated, on the
+ *     device -- the reference's (n_valid * 0.1).long(), an int64 tensor times a Python float;
+ *   mean and unbiased variance (fp64 sums) of the participating values of rank [lo, hi), ties counted by rank;
+ *   mask byte non-zero:  y = (x - (float)mean) * (1 / sqrtf((float)var + eps))   (a valid NaN stays a NaN by arithmetic);
+ *   mask byte zero:      y = +0, stored, never a product: NaN or inf under the mask give 0;
+ *   hi - lo < 2 (an empty slice, or one value, whose var() is NaN): NaN at every mask-true element, 0 elsewhere.
+ * With every element taking part the result is bit-identical to mmae_depth_standardize with the same cuts (one kernel
+ * template, one thread-to-element mapping, one reduction order).  MMAE_EINVAL, nothing written: x or y NULL, B <= 0,
+ * n < 1 or n > 2^24 (where (float)n_valid stops being exact), fractions not 0 <= lo_frac <= hi_frac <= 1, a NaN
+ * fraction or eps.
+ *
+ * mmae_mask_invalid is the masking of the other non-rgb inputs (run_finetuning_depth.py:690-695, one task of the loop;
+ * the Taskonomy script: :663-668, :784-789) without the (B, C, H, W) boolean temporary: in place on x f32 [B][C][n] with
+ * mask [B][n], x[b][c][i] = mask[b][i] ? x[b][c][i] : +0.  A valid element keeps its bits (-0, NaN payloads), an invalid
+ * one becomes +0 whatever it held.  One launch.
+ * ------------------------------------------------------------------------- */
+int mmae_depth_standardize_masked(const float* x, const uint8_t* mask, float* y, int B, int n, float lo_frac, float hi_frac, float eps,
+                                  void* stream);
+int mmae_mask_invalid(float* x, const uint8_t* mask, int B, int C, int n, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * On-device ingest of a host-decoded batch (multimae_amd/staging.py): the conversions utils/datasets.py:93-107
  * (DataAugmentationForMultiMAE) makes on the host, applied after the H2D copy of the compact arrays the decoder produced, so
  * 65 MB cross PCIe per cfg3 batch of 256 instead of 212 MB.  Every result is bit-identical to the host conversion.

@@ -6,7 +6,7 @@ SpatialOutputAdapter; plus the engine controls (precision, parameter arena, fuse
 data-parallel gradient reducer) and the batch stager (host batches copied on their own stream, decoded on the device).
 """
 from . import engine  # noqa: F401
-from .data_ops import truncated_depth_standardize  # noqa: F401
+from .data_ops import mask_invalid_, robust_depth_standardize, robust_depth_standardize_, truncated_depth_standardize  # noqa: F401
 from .criterion import (LabelSmoothingCrossEntropy, MaskedCrossEntropyLoss, MaskedL1Loss, MaskedMSELoss,  # noqa: F401
                         SegCrossEntropyLoss, SoftTargetCrossEntropy, masked_berhu_loss, masked_l1_loss, masked_mse_loss)
 from .ema import ModelEma  # noqa: F401

@@ -5,6 +5,10 @@ every depth map each step -- with one selection kernel (``mmae_depth_standardize
 
     if standardize_depth and 'depth' in tasks_dict:
         tasks_dict['depth'] = truncated_depth_standardize(tasks_dict['depth'])
+
+``robust_depth_standardize`` / ``mask_invalid_`` are the mask-aware form of the fine-tuning loops (run_finetuning_depth.py:671-695,
+run_finetuning_taskonomy.py:645-668): ``mmae_depth_standardize_masked`` and ``mmae_mask_invalid`` of the same file, one launch each,
+the cuts taken from the count of valid pixels on the device.  ``dropin/amd_loop.prepare_dense_inputs`` is the loop's call site.
 """
 from __future__ import annotations
 
@@ -92,6 +96,66 @@ def depth_standardize_(x: torch.Tensor, lo: float = 0.1, hi: float = 0.9, eps: f
     n = x.numel() // B
     _lib.check(_lib.load().mmae_depth_standardize(x.data_ptr(), x.data_ptr(), B, n, int(lo * n), int(hi * n), eps, ops._stream()),
                'depth_standardize')
+    return x
+
+
+def _dense_f32(x, what, name='input'):
+    if not isinstance(x, torch.Tensor) or not ops._device_ok(x) or x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        got = f'{tuple(x.shape)} {x.dtype} on {x.device}' if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f'{what}: {name} must be a contiguous f32 (B, C, H, W) tensor on the GPU, got {got}')
+    if x.numel() == 0:
+        raise ValueError(f'{what}: {name} is empty, {tuple(x.shape)}')
+
+
+def _valid_mask(mask, like, what):
+    """a contiguous torch.bool (B, 1, H, W) mask on ``like``'s device"""
+    shape = (like.shape[0], 1, like.shape[2], like.shape[3])
+    if (not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or tuple(mask.shape) != shape or mask.device != like.device
+            or not mask.is_contiguous()):
+        got = f'{tuple(mask.shape)} {mask.dtype} on {mask.device}' if isinstance(mask, torch.Tensor) else type(mask).__name__
+        raise ValueError(f'{what}: mask_valid must be a contiguous torch.bool tensor of shape {shape} on {like.device}, got {got}')
+    return mask
+
+
+def _robust(depth, mask_valid, lo, hi, eps, out, what):
+    _dense_f32(depth, what, 'depth')
+    if depth.shape[1] != 1:
+        raise ValueError(f'{what}: depth must have one channel, got {tuple(depth.shape)}')
+    if mask_valid is not None:
+        _valid_mask(mask_valid, depth, what)
+    B, n = depth.shape[0], depth.shape[2] * depth.shape[3]
+    _lib.check(_lib.load().mmae_depth_standardize_masked(depth.data_ptr(), None if mask_valid is None else mask_valid.data_ptr(),
+                                                         out.data_ptr(), B, n, lo, hi, eps, ops._stream()), what)
+    return out
+
+
+def robust_depth_standardize(depth: torch.Tensor, mask_valid: torch.Tensor = None, lo: float = 0.1, hi: float = 0.9, eps: float = 1e-6,
+                             out: torch.Tensor = None) -> torch.Tensor:
+    """run_finetuning_depth.py:672-688 in one launch: ``depth`` f32 (B, 1, H, W), ``mask_valid`` bool of the same shape (None: all
+    valid).  Per sample the mean and unbiased variance of the valid, non-NaN values of rank [int(n_valid * lo), int(n_valid * hi))
+    -- the count and the cuts stay on the device -- then ``(depth - mean) / sqrt(var + eps)`` where the mask is set and 0 elsewhere;
+    fewer than two values in the slice: NaN where the mask is set, as the reference.  Returns a new tensor (or ``out``); ``depth``
+    is not written: the loop's ``tasks_dict['depth']``, the loss target, is the same object and stays raw."""
+    what = 'robust_depth_standardize'
+    _dense_f32(depth, what, 'depth')
+    out = _out(out, tuple(depth.shape), torch.float32, depth.device, what)
+    return _robust(depth, mask_valid, lo, hi, eps, out, what)
+
+
+def robust_depth_standardize_(depth: torch.Tensor, mask_valid: torch.Tensor = None, lo: float = 0.1, hi: float = 0.9,
+                              eps: float = 1e-6) -> torch.Tensor:
+    """``robust_depth_standardize`` in place (the kernel allows y to alias x)."""
+    return _robust(depth, mask_valid, lo, hi, eps, depth, 'robust_depth_standardize_')
+
+
+def mask_invalid_(x: torch.Tensor, mask_valid: torch.Tensor) -> torch.Tensor:
+    """run_finetuning_depth.py:694-695 for one task, in place and without the (B, C, H, W) boolean temporary: ``x`` f32 (B, C, H, W),
+    ``mask_valid`` bool (B, 1, H, W); ``x[b, c, h, w] = 0`` where ``mask_valid[b, 0, h, w]`` is False, untouched elsewhere."""
+    what = 'mask_invalid_'
+    _dense_f32(x, what, 'x')
+    _valid_mask(mask_valid, x, what)
+    B, C, H, W = x.shape
+    _lib.check(_lib.load().mmae_mask_invalid(x.data_ptr(), mask_valid.data_ptr(), B, C, H * W, ops._stream()), what)
     return x
 
 
