@@ -1009,6 +1009,37 @@ int mmae_resize_fwd(const float* x, int64_t ldx, float* out, int B, int h, int w
 int mmae_resize_bwd(const float* g, float* dx, int64_t ldx, int B, int h, int w, int K, int H, int W, int mode, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Dense 3 x 3 convolutions and the x2 upsample of the DPT head's RefineNet fusion blocks, csrc/conv3x3.hip.  Replaces the
+ * nn.Conv2d(kernel_size=3, padding=1, stride 1 | 2, groups=1) of ResidualConvUnit_custom (output_adapter_utils.py:74-92,110-123),
+ * make_scratch (output_adapter_utils.py:138-173), the DPT regression and semseg heads (output_adapters.py:628,630,637) and the
+ * stride-2 convolution of act_4_postprocess (output_adapters.py:703-707), and the F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) of
+ * FeatureFusionBlock_custom.forward (output_adapter_utils.py:241-243; the heads' Interpolate, output_adapters.py:629,642), with every autograd product of them.
+ * Maps are channels-last f32 [n][h][w][C] as in the ConvNeXt head; ho = (h - 1) / stride + 1, wo likewise.  A convolution is
+ * im2col + mmae_gemm (bias and the residual add in the GEMM epilogue); its weight gradient is the GEMM dY^T x col, its data
+ * gradient the GEMM dY x W followed by col2im.  No float atomics; results are bit-equal from run to run.
+ *   im2col:        col[(b ho + oy) wo + ox][(ky 3 + kx) C + c] = x[b][oy stride + ky - 1][ox stride + kx - 1][c], 0 at padded taps;
+ *                  relu != 0: max(x, 0) of the values read (x itself is not modified).  col_dtype MMAE_BF16 (C % 8 == 0, 16-byte
+ *                  aligned pointers: eight channels per thread, 16-byte loads and stores) or MMAE_F32 (any C).
+ *   col2im:        dx[b][iy][ix][c] = m * sum_(ky, kx) dcol[(b ho + oy) wo + ox][(ky 3 + kx) C + c] + addend[b][iy][ix][c] over the (at
+ *                  most nine) taps with oy stride + ky - 1 == iy and ox stride + kx - 1 == ix, ky then kx ascending; m = (xmask > 0)
+ *                  element-wise (the ReLU of im2col; NULL: 1), addend NULL: 0 (the gradient of a residual branch).  dcol f32.
+ *   weight_pack:   wp[o][(ky 3 + kx) Cin + c] = w[o][c][ky][kx]: nn.Conv2d's (Cout, Cin, 3, 3) f32 weight as the [Cout][9 Cin] GEMM
+ *                  operand in wp_dtype (MMAE_F32 | MMAE_BF16), permuted and rounded in one pass.
+ *   weight_unpack: the way back for the gradient: dw[o][c][ky][kx] (+)= dwp[o][(ky 3 + kx) Cin + c], both f32.
+ *   upsample2x_fwd: y f32 [B][2h][2w][C] from x f32 [B][h][w][C] with PyTorch's align_corners = True source index
+ *                  dst * (in - 1) / (out - 1); a one-pixel input is replicated.
+ *   upsample2x_bwd: its backward as a gather, every input element summing its output window in a fixed order (rows ascending, within
+ *                  a row columns ascending): g f32 [B][2h][2w][C] -> dx f32 [B][h][w][C].
+ * ------------------------------------------------------------------------- */
+int mmae_conv3x3_im2col(const float* x, void* col, int col_dtype, int n, int h, int w, int C, int stride, int relu, void* stream);
+int mmae_conv3x3_col2im(const float* dcol, const float* xmask, const float* addend, float* dx, int n, int h, int w, int C, int stride,
+                        void* stream);
+int mmae_conv3x3_weight_pack(const float* w, void* wp, int wp_dtype, int Cout, int Cin, void* stream);
+int mmae_conv3x3_weight_unpack(const float* dwp, float* dw, int Cout, int Cin, int accumulate, void* stream);
+int mmae_upsample2x_fwd(const float* x, float* y, int B, int h, int w, int C, void* stream);
+int mmae_upsample2x_bwd(const float* g, float* dx, int B, int h, int w, int C, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Semantic-segmentation loss and metrics on the head's low-resolution logits, csrc/segloss.hip: the (B, K, H, W) image of
  * mmae_resize_fwd is never read.  x f32 [B][h][w][ldx] (first K columns), target / pred / label int64 [B][H][W], mode as in
  * mmae_resize_fwd (every geometry it takes is taken here), the interpolated value bit-identical to the pixel it would store.  A target

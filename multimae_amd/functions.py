@@ -1455,3 +1455,260 @@ class SoftCEFn(torch.autograd.Function):
         up = g.contiguous().float().reshape(1)
         dx = ops.soft_ce_bwd(x, K, B, K, target, labels, ctx.smoothing, lse, tsum, up, torch.empty_like(x))
         return dx, None, None, None
+
+
+# ------------------------------------------------------------------------------------------
+# Dense 3 x 3 convolutions and the RefineNet fusion blocks of the DPT head (output_adapter_utils.py:60-257) on csrc/conv3x3.hip
+# ------------------------------------------------------------------------------------------
+def _nhwc(x: Tensor) -> Tensor:
+    """(B, C, H, W)-shaped tensor -> its f32 [B, H, W, C] map: a view when x is contiguous in torch.channels_last (physically NHWC
+    already), one conversion otherwise."""
+    return x.detach().float().permute(0, 2, 3, 1).contiguous()
+
+
+def _col_rows(B: int, rows: int, K9: int, esize: int, cap: int) -> int:
+    """samples per chunk such that the gathered rows of a chunk stay within `cap` bytes (one sample at least)"""
+    return max(1, min(B, int(cap) // max(1, rows * K9 * esize)))
+
+
+def _col_buffer(like: Tensor, nbytes: int) -> Tensor:
+    """the gathered rows of one chunk, as f32 elements: taken from the allocator per convolution, as the ConvNeXt head takes its buffers
+    (every chunk of the call reuses it; the launches that read and write it follow one another on the stream)"""
+    return torch.empty(((nbytes + 3) // 4,), device=like.device, dtype=torch.float32)
+
+
+def conv3x3_fwd(x: Tensor, wp: Tensor, bias: Optional[Tensor], stride: int, relu: bool, resid: Optional[Tensor], cap: int) -> Tensor:
+    """y [B, ho, wo, Cout] f32 = conv3x3(relu?(x)) + bias + resid on the f32 NHWC map x: per chunk of samples one im2col gather and one
+    GEMM against the packed weight wp [Cout, 9 Cin] (bias and residual in the GEMM's epilogue)."""
+    B, h, w, Cin = x.shape
+    Cout, K9 = wp.shape
+    ho, wo = ops.conv_out_size(h, stride), ops.conv_out_size(w, stride)
+    R1 = ho * wo
+    if K9 != 9 * Cin or (resid is not None and tuple(resid.shape) != (B, ho, wo, Cout)):
+        raise ValueError(f'conv3x3_fwd: a {tuple(x.shape)} map does not fit the [{Cout}, {K9}] packed weight'
+                         + ('' if resid is None else f' and the {tuple(resid.shape)} residual'))
+    y = _new((B, ho, wo, Cout), x, torch.float32)
+    y2 = y.view(B * R1, Cout)
+    r2 = resid.view(B * R1, Cout) if resid is not None else None
+    esz = wp.element_size()
+    nb = _col_rows(B, R1, K9, esz, cap)
+    ws = _col_buffer(x, nb * R1 * K9 * esz)
+    for b0 in range(0, B, nb):
+        n = min(nb, B - b0)
+        col = ws.view(wp.dtype)[:n * R1 * K9].view(n * R1, K9)
+        ops.conv3x3_im2col(x[b0:], col, n, h, w, Cin, stride, relu)
+        ops.gemm(col, wp, y2[b0 * R1:], n * R1, Cout, K9, lda=K9, ldb=K9, ldc=Cout, bias=bias,
+                 resid=None if r2 is None else r2[b0 * R1:], ldr=Cout)
+    return y
+
+
+def conv3x3_bwd(dy: Tensor, x: Tensor, wp: Tensor, stride: int, relu: bool, addend: Optional[Tensor], cap: int, need_dx: bool,
+                need_dw: bool):
+    """Gradients of conv3x3_fwd for dy [B, ho, wo, Cout] f32: (dx [B, h, w, Cin] f32 = relu'(x) * conv^T(dy) + addend, dwp [Cout, 9 Cin]
+    f32 in the packed order), None where not needed.  Per chunk: the gathered rows are recomputed (never saved) for dY^T x col,
+    then the same buffer takes dY x W, which col2im gathers into dx."""
+    B, h, w, Cin = x.shape
+    Cout, K9 = wp.shape
+    ho, wo = ops.conv_out_size(h, stride), ops.conv_out_size(w, stride)
+    R1 = ho * wo
+    if K9 != 9 * Cin or tuple(dy.shape) != (B, ho, wo, Cout) or (addend is not None and addend.shape != x.shape):
+        raise ValueError(f'conv3x3_bwd: a {tuple(dy.shape)} gradient and a {tuple(x.shape)} map do not fit the [{Cout}, {K9}] packed weight'
+                         + ('' if addend is None else f' and the {tuple(addend.shape)} addend'))
+    f32 = torch.float32
+    dya = ops.cast(dy.reshape(B * R1, Cout), wp.dtype)
+    dx = _new((B, h, w, Cin), x, f32) if need_dx else None
+    dwp = _new((Cout, K9), x, f32) if need_dw else None
+    esz = 4 if need_dx else wp.element_size()
+    nb = _col_rows(B, R1, K9, esz, cap)
+    ws = _col_buffer(x, nb * R1 * K9 * esz)
+    for b0 in range(0, B, nb):
+        n = min(nb, B - b0)
+        d = dya[b0 * R1:(b0 + n) * R1]
+        if need_dw:
+            col = ws.view(wp.dtype)[:n * R1 * K9].view(n * R1, K9)
+            ops.conv3x3_im2col(x[b0:], col, n, h, w, Cin, stride, relu)
+            ops.linear_dw(d, col, dwp, b0 > 0)
+        if need_dx:
+            dcol = ws[:n * R1 * K9].view(n * R1, K9)
+            ops.linear_dx(d, wp, dcol)
+            ops.conv3x3_col2im(dcol, x[b0:] if relu else None, None if addend is None else addend[b0:], dx[b0:], n, h, w, Cin, stride)
+    return dx, dwp
+
+
+def _conv_wgrad(sink: GradSink, p: Tensor, dwp: Optional[Tensor]):
+    """the packed weight gradient into p's (Cout, Cin, 3, 3) gradient: stored into a fresh tensor, or accumulated into the arena"""
+    if dwp is None or not p.requires_grad:
+        return None
+    tgt, acc = sink._target(p)
+    if sink.side is not None and acc:
+        sink._on_side(lambda: ops.conv3x3_weight_unpack(dwp, tgt, True), dwp)
+    else:
+        ops.conv3x3_weight_unpack(dwp, tgt, acc)
+    return None if acc else tgt
+
+
+def _check_map(what: str, x: Tensor, channels: int, name: str = 'input'):
+    """the geometry nn.Conv2d would refuse: a (B, C, H, W)-shaped tensor with the channel count the weights were built for.  (The
+    gathered rows are sized from the weight, so a wrong channel count must never reach the kernels.)"""
+    if x.dim() != 4 or x.shape[1] != channels or x.numel() == 0:
+        raise ValueError(f'{what}: the {name} has shape {tuple(x.shape)}; the module takes a non-empty (B, {channels}, H, W) tensor')
+
+
+def _check_conv(cfg: _Cfg, what: str, *channels: int):
+    if cfg.act != torch.float32 and any(c % 8 for c in channels):
+        raise ValueError(f'{what}: the bf16 gather and GEMMs need channel counts that are multiples of 8 (got {channels}); use '
+                         'engine.set_precision("fp32") for this geometry')
+
+
+class Conv3x3Fn(torch.autograd.Function):
+    """nn.Conv2d(kernel_size=3, padding=1, stride 1 | 2) as ONE autograd node: (B, Cin, H, W) -> (B, Cout, ho, wo), f32, the output
+    channels-last strided.  cfg: act, stride, cap (bytes of gathered rows per chunk)."""
+
+    @staticmethod
+    def forward(ctx, cfg: _Cfg, x: Tensor, w: Tensor, b: Optional[Tensor]):
+        ops._require_gpu(x, 'Conv3x3 input')
+        _check_map('Conv3x3', x, w.shape[1])
+        _check_conv(cfg, 'Conv3x3', w.shape[1], w.shape[0])
+        xn = _nhwc(x)
+        wp = ops.conv3x3_weight_pack(w.detach().contiguous(), cfg.act)
+        y = conv3x3_fwd(xn, wp, None if b is None else b.detach(), cfg.stride, False, None, cfg.cap)
+        ctx.cfg, ctx.saved, ctx.params = cfg, (xn, wp), (w, b)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        cfg, (xn, wp), (w, b) = ctx.cfg, ctx.saved, ctx.params
+        sink = GradSink(engine.direct_grads())
+        g = _nhwc(dy)
+        dx, dwp = conv3x3_bwd(g, xn, wp, cfg.stride, False, None, cfg.cap, ctx.needs_input_grad[1], w.requires_grad)
+        gw = _conv_wgrad(sink, w, dwp)
+        gb = sink.bias(b, g.view(-1, g.shape[-1])) if b is not None else None
+        ctx.saved = ctx.params = None
+        return None, (dx.permute(0, 3, 1, 2) if dx is not None else None), gw, gb
+
+
+def _rcu_fwd(x: Tensor, wps, params, cap: int):
+    """ResidualConvUnit_custom.forward (output_adapter_utils.py:110-123) on the NHWC map: conv2(relu(conv1(relu(x)))) + x.  The ReLUs
+    are applied by the gathers (x stays un-activated for the residual), the residual add is conv2's GEMM epilogue."""
+    c1w, c1b, c2w, c2b = params
+    t = conv3x3_fwd(x, wps[0], c1b.detach(), 1, True, None, cap)
+    y = conv3x3_fwd(t, wps[1], c2b.detach(), 1, True, x, cap)
+    return y, t
+
+
+def _rcu_bwd(dy: Tensor, x: Tensor, t: Tensor, wps, params, sink: GradSink, cap: int, need_dx: bool):
+    """(dx, [g conv1.weight, g conv1.bias, g conv2.weight, g conv2.bias]) of _rcu_fwd"""
+    c1w, c1b, c2w, c2b = params
+    C = dy.shape[-1]
+    dt, dwp2 = conv3x3_bwd(dy, t, wps[1], 1, True, None, cap, True, c2w.requires_grad)
+    g2w, g2b = _conv_wgrad(sink, c2w, dwp2), sink.bias(c2b, dy.view(-1, C))
+    dx, dwp1 = conv3x3_bwd(dt, x, wps[0], 1, True, dy, cap, need_dx, c1w.requires_grad)       # + dy: the skip connection
+    g1w, g1b = _conv_wgrad(sink, c1w, dwp1), sink.bias(c1b, dt.view(-1, C))
+    return dx, [g1w, g1b, g2w, g2b]
+
+
+class ResidualConvUnitFn(torch.autograd.Function):
+    """ResidualConvUnit_custom as ONE autograd node.  params: conv1.{weight, bias}, conv2.{weight, bias}."""
+
+    @staticmethod
+    def forward(ctx, cfg: _Cfg, x: Tensor, *params: Tensor):
+        ops._require_gpu(x, 'ResidualConvUnit_custom input')
+        _check_map('ResidualConvUnit_custom', x, params[0].shape[1])
+        _check_conv(cfg, 'ResidualConvUnit_custom', params[0].shape[1])
+        xn = _nhwc(x)
+        wps = [ops.conv3x3_weight_pack(params[i].detach().contiguous(), cfg.act) for i in (0, 2)]
+        y, t = _rcu_fwd(xn, wps, params, cfg.cap)
+        ctx.cfg, ctx.saved, ctx.params = cfg, (xn, t, wps), params
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        xn, t, wps = ctx.saved
+        sink = GradSink(engine.direct_grads())
+        dx, grads = _rcu_bwd(_nhwc(dy), xn, t, wps, ctx.params, sink, ctx.cfg.cap, ctx.needs_input_grad[1])
+        ctx.saved = ctx.params = None
+        return (None, (dx.permute(0, 3, 1, 2) if dx is not None else None), *grads)
+
+
+class FusionBlockFn(torch.autograd.Function):
+    """FeatureFusionBlock_custom.forward (output_adapter_utils.py:227-247) as ONE autograd node: x0 (+ resConfUnit1(x1)) ->
+    resConfUnit2 -> bilinear x2 (align_corners=True) -> the 1 x 1 out_conv (a row GEMM with its bias).  x1 may be None.
+    params: out_conv.{weight, bias}, resConfUnit1.conv1.{weight, bias}, .conv2.{weight, bias}, resConfUnit2 likewise."""
+
+    @staticmethod
+    def forward(ctx, cfg: _Cfg, x0: Tensor, x1: Optional[Tensor], *params: Tensor):
+        ops._require_gpu(x0, 'FeatureFusionBlock_custom input')
+        act = cfg.act
+        ow, ob = params[0], params[1]
+        Co, C = ow.shape[0], ow.shape[1]
+        _check_map('FeatureFusionBlock_custom', x0, C, 'first input')
+        if x1 is not None:
+            _check_map('FeatureFusionBlock_custom', x1, C, 'second input')
+            if x1.shape != x0.shape:
+                raise ValueError(f'FeatureFusionBlock_custom: the two inputs differ in shape ({tuple(x0.shape)}, {tuple(x1.shape)})')
+        _check_conv(cfg, 'FeatureFusionBlock_custom', C, Co)
+        a = _nhwc(x0)
+        B, h, w, _ = a.shape
+        pack = lambda i: [ops.conv3x3_weight_pack(params[j].detach().contiguous(), act) for j in (i, i + 2)]
+        wps1 = t1 = b = None
+        s = a
+        if x1 is not None:
+            b = _nhwc(x1)
+            wps1 = pack(2)
+            s, t1 = _rcu_fwd(b, wps1, params[2:6], cfg.cap)
+            ops.axpy_(s, a, 1.0)                                          # output = xs[0] + resConfUnit1(xs[1])
+        wps2 = pack(6)
+        u, t2 = _rcu_fwd(s, wps2, params[6:10], cfg.cap)
+        up = ops.upsample2x_fwd(u, B, h, w, C)
+        del u
+        R = B * 4 * h * w
+        upa = ops.cast(up.view(R, C), act)
+        del up
+        y = _new((B, 2 * h, 2 * w, Co), a, torch.float32)
+        ops.gemm(upa, cfg.wc(ow).view(Co, C), y.view(R, Co), R, Co, C, lda=C, ldb=C, ldc=Co, bias=ob.detach())
+        ctx.cfg, ctx.params = cfg, params
+        ctx.saved = (b, t1, wps1, s, t2, wps2, upa, (B, h, w, C, Co))
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        cfg, params = ctx.cfg, ctx.params
+        b, t1, wps1, s, t2, wps2, upa, (B, h, w, C, Co) = ctx.saved
+        act = cfg.act
+        sink = GradSink(engine.direct_grads())
+        ow, ob = params[0], params[1]
+        R = B * 4 * h * w
+        grads: List[Optional[Tensor]] = [None] * len(params)
+        g = _nhwc(dy).view(R, Co)
+        ga = ops.cast(g, act)
+        d_up = ops.linear_dx(ga, cfg.wc(ow).view(Co, C), _new((R, C), g, torch.float32))
+        grads[0], grads[1] = sink.linear(ow, ob, ga, upa)
+        du = ops.upsample2x_bwd(d_up, B, h, w, C)
+        del d_up
+        need1 = b is not None and ctx.needs_input_grad[2]
+        ds, grads[6:10] = _rcu_bwd(du, s, t2, wps2, params[6:10], sink, cfg.cap, ctx.needs_input_grad[1] or b is not None)
+        dx1 = None
+        if b is not None:
+            dx1, grads[2:6] = _rcu_bwd(ds, b, t1, wps1, params[2:6], sink, cfg.cap, need1)
+        ctx.saved = ctx.params = None
+        dx0 = ds.permute(0, 3, 1, 2) if (ds is not None and ctx.needs_input_grad[1]) else None
+        return (None, dx0, (dx1.permute(0, 3, 1, 2) if dx1 is not None else None), *grads)
+
+
+class Upsample2xFn(torch.autograd.Function):
+    """F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) on a (B, C, H, W)-shaped f32 tensor, channels-last inside"""
+
+    @staticmethod
+    def forward(ctx, x: Tensor):
+        ops._require_gpu(x, 'Interpolate input')
+        if x.dim() != 4 or x.numel() == 0:
+            raise ValueError(f'Interpolate: the input has shape {tuple(x.shape)}; the module takes a non-empty (B, C, H, W) tensor')
+        xn = _nhwc(x)
+        ctx.geom = tuple(xn.shape)
+        B, h, w, C = xn.shape
+        return ops.upsample2x_fwd(xn, B, h, w, C).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        B, h, w, C = ctx.geom
+        return ops.upsample2x_bwd(_nhwc(dy), B, h, w, C).permute(0, 3, 1, 2)

@@ -1555,6 +1555,65 @@ def resize_bwd(g: Tensor, dx: Tensor, ldx: int, B: int, h: int, w: int, K: int, 
     return dx
 
 
+# ------------------------------------------- dense 3 x 3 convolutions and the x2 upsample of the fusion blocks (csrc/conv3x3.hip) --
+def conv_out_size(n: int, stride: int) -> int:
+    """output extent of a 3 x 3, padding 1 convolution"""
+    return (n - 1) // stride + 1
+
+
+def conv3x3_im2col(x: Tensor, col: Tensor, n: int, h: int, w: int, C: int, stride: int, relu: bool) -> Tensor:
+    """x f32 [n, h, w, C] -> col [n ho wo, 9 C] (bf16 or f32) in (ky, kx, c) order, zeros at padded taps, optional ReLU on the fly"""
+    rows = n * conv_out_size(h, stride) * conv_out_size(w, stride)
+    if x.dtype != torch.float32 or x.numel() < n * h * w * C or col.numel() < rows * 9 * C:
+        raise ValueError(f'conv3x3_im2col: {n} x {h} x {w} x {C} f32 samples need {rows * 9 * C} elements of gathered rows; got a map of '
+                         f'{x.numel()} {x.dtype} elements and room for {col.numel()}')
+    check(_lib.load().mmae_conv3x3_im2col(x.data_ptr(), col.data_ptr(), dcode(col.dtype), n, h, w, C, stride, int(relu), _stream()), 'conv3x3_im2col')
+    return col
+
+
+def conv3x3_col2im(dcol: Tensor, xmask: Optional[Tensor], addend: Optional[Tensor], dx: Tensor, n: int, h: int, w: int, C: int,
+                   stride: int) -> Tensor:
+    """dcol f32 [n ho wo, 9 C] -> dx f32 [n, h, w, C] = (xmask > 0) * (sum of each pixel's taps) + addend"""
+    rows, pix = n * conv_out_size(h, stride) * conv_out_size(w, stride), n * h * w * C
+    if (dcol.dtype != torch.float32 or dx.dtype != torch.float32 or dcol.numel() < rows * 9 * C or dx.numel() < pix
+            or any(t is not None and (t.dtype != torch.float32 or t.numel() < pix) for t in (xmask, addend))):
+        raise ValueError(f'conv3x3_col2im: {n} x {h} x {w} x {C} samples need {rows * 9 * C} f32 elements of rows and {pix} per map; got '
+                         f'{dcol.numel()} and {[None if t is None else t.numel() for t in (dx, xmask, addend)]}')
+    check(_lib.load().mmae_conv3x3_col2im(dcol.data_ptr(), _p(xmask), _p(addend), dx.data_ptr(), n, h, w, C, stride, _stream()), 'conv3x3_col2im')
+    return dx
+
+
+def conv3x3_weight_pack(w: Tensor, dtype: torch.dtype) -> Tensor:
+    """nn.Conv2d's (Cout, Cin, 3, 3) f32 weight -> the [Cout, 9 Cin] GEMM operand in (ky, kx, c) order, rounded to `dtype`"""
+    Cout, Cin = w.shape[0], w.shape[1]
+    assert w.dtype == torch.float32 and tuple(w.shape[2:]) == (3, 3) and w.is_contiguous()
+    wp = torch.empty((Cout, 9 * Cin), device=w.device, dtype=dtype)
+    check(_lib.load().mmae_conv3x3_weight_pack(w.data_ptr(), wp.data_ptr(), dcode(dtype), Cout, Cin, _stream()), 'conv3x3_weight_pack')
+    return wp
+
+
+def conv3x3_weight_unpack(dwp: Tensor, dw: Tensor, accumulate: bool) -> Tensor:
+    """dw (Cout, Cin, 3, 3) f32 (+)= the [Cout, 9 Cin] gradient in the packed order"""
+    Cout, Cin = dw.shape[0], dw.shape[1]
+    assert dwp.dtype == torch.float32 and dw.dtype == torch.float32 and dw.is_contiguous() and dwp.numel() == dw.numel()
+    check(_lib.load().mmae_conv3x3_weight_unpack(dwp.data_ptr(), dw.data_ptr(), Cout, Cin, int(accumulate), _stream()), 'conv3x3_weight_unpack')
+    return dw
+
+
+def upsample2x_fwd(x: Tensor, B: int, h: int, w: int, C: int) -> Tensor:
+    """F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) on the f32 NHWC map"""
+    y = torch.empty((B, 2 * h, 2 * w, C), device=x.device, dtype=torch.float32)
+    check(_lib.load().mmae_upsample2x_fwd(x.data_ptr(), y.data_ptr(), B, h, w, C, _stream()), 'upsample2x_fwd')
+    return y
+
+
+def upsample2x_bwd(g: Tensor, B: int, h: int, w: int, C: int) -> Tensor:
+    """its backward: g f32 [B, 2h, 2w, C] -> dx f32 [B, h, w, C]"""
+    dx = torch.empty((B, h, w, C), device=g.device, dtype=torch.float32)
+    check(_lib.load().mmae_upsample2x_bwd(g.data_ptr(), dx.data_ptr(), B, h, w, C, _stream()), 'upsample2x_bwd')
+    return dx
+
+
 # ------------------------------------------------- segmentation loss and metrics on the low-resolution logits (csrc/segloss.hip) --
 SEG_PARTIALS = 2048          # MMAE_SEG_PARTIALS: rows of the forward's per-workgroup (sum, count) scratch
 SEG_HIST_MAX_K = 4096        # MMAE_SEG_HIST_MAX_K
