@@ -431,8 +431,13 @@ int mmae_attn_bwd_tiled(const void* q, const void* k, const void* v, const void*
  * One pre-LN transformer block (multimae_utils.py:217-232: x + attn(norm1(x)), then x + mlp(norm2(x))) as ONE call per
  * direction: the library enqueues the block's whole kernel sequence (forward 7 launches; backward ~20, with the
  * weight-gradient GEMMs and the parameter-gradient reductions on `side_stream`, ordered against `stream` with events).
- * Same kernels, same order and same results as issuing the individual entry points; what it removes is ~25 host
- * round trips per block (the host, not the GPU, paced the adapters' backward passes).
+ * Same mathematics as issuing the individual entry points, and the same kernels for every activation and input gradient; what
+ * it removes is ~25 host round trips per block (the host, not the GPU, paced the adapters' backward passes).  Parameter gradients
+ * may differ from the one-by-one sequence in their last bits: with 16-bit activations the block's weight gradients (and the bias
+ * gradients they carry) come from ONE grouped launch (mmae_gemm_dw_group) and the remaining column sums from ONE batched launch
+ * (mmae_colsum_batch), at D = 256 a LayerNorm may be the side output of the product in front of it (mmae_ln_fuse), and bf16 keeps
+ * GELU'(pre-activation) instead of the pre-activation in `hpre` (mmae_gelu_grad_aux).  Every reduction is fixed-order: a call repeats
+ * bit for bit, on one stream or two, and a requested gradient does not depend on which other destinations are NULL.
  * Every buffer is the caller's: activations (forward writes, backward reads), backward temporaries, gradient
  * destinations, and two f32 workspaces (split-K slabs / reduction scratch) private to the two streams.
  * act_dtype MMAE_BF16, or MMAE_F32 with f32_gemm = MMAE_F32X3 (fp32 adapters in speed mode).  Needs the fused attention
@@ -459,7 +464,11 @@ typedef struct mmae_block_desc {
     int32_t grad_acc;                            /* gradients are added to (1) or stored into (0) their destinations */
     int32_t fc2_b_done;                          /* the producer of dx already delivered fc2's bias gradient: skip it */
     float* ws_main; int64_t ws_main_elems;       /* f32 scratch used by launches on `stream` */
-    float* ws_side; int64_t ws_side_elems;       /* f32 scratch used by launches on `side_stream` */
+    float* ws_side; int64_t ws_side_elems;       /* f32 scratch used by launches on `side_stream`: the slabs of the grouped weight-gradient
+                                                    launch (mmae_gemm_dw_group_ws_elems) -- plus n_out * k_in floats for every Linear whose bias
+                                                    gradient is wanted WITHOUT its weight gradient (the product still runs in the group, its dW
+                                                    discarded, so that the bias gradient's bits do not depend on the weight's destination) --
+                                                    or the largest single split-K / column-sum need; too little is refused with MMAE_EINVAL */
     /* stochastic depth (DropPath, multimae_utils.py:105-135,229-232): per-sample scales f32 [B] = mask_b / keep_prob of the
      * attention branch (dp1) and the MLP branch (dp2); NULL = branch kept for every sample.  x1 = x0 + dp1[b] * attn(..),
      * x2 = x1 + dp2[b] * mlp(..).  With a scale set, `branch` (f32 [R][D], forward) and `dxs_act` (act [R][D], backward)
@@ -535,8 +544,9 @@ int mmae_stack_bwd(const mmae_stack_desc* d, void* stream, void* side_stream);
 /* ------------------------------------------------------------------------- *
  * SpatialOutputAdapter.forward (output_adapters.py:236-282) and its autograd as ONE call per direction: proj_context,
  * query / context build (:183-234), the cross-attention layer with its MLP (:262-266), the decoder_transformer blocks
- * (:271), out_proj (:274) and the patch -> image rearrangement (:277-280).  Same kernels and order as the individual
- * entry points; ~45 host round trips forward and ~125 backward become one each.
+ * (:271), out_proj (:274) and the patch -> image rearrangement (:277-280).  Same mathematics as the individual entry points
+ * (launch substitutions as listed at mmae_block_desc: grouped weight gradients, batched column sums, LayerNorm side outputs and
+ * the fused row build + LayerNorm at D <= 256); ~45 host round trips forward and ~125 backward become one each.
  *   enc      f32 [B][NC][Denc] encoder tokens (NC = n_keep + G); enc_act: their act-dtype copy (== enc when act is f32)
  *   w        host array [6 + 4*depth] act-dtype weights: q, kv, proj, fc1, fc2, then per block qkv, proj, fc1, fc2,
  *            then out_proj; proj_context LAST

@@ -292,22 +292,30 @@ bool dw_group_enabled() {
 struct DwGroup {
     mmae_dw_group_desc g;
     bool on;
+    int64_t scratch = 0;     // f32 elements of throw-away dW (problems queued for their bias gradient alone)
     DwGroup(const Ctx& c, int rows) : g{}, on(c.b16() && (dw_group_enabled() || c.h16())) {
         g.rows = rows; g.ab_dtype = c.act_dtype; g.accumulate = c.grad_acc; g.unscale = c.unscale();
     }
-    // queue dw (+ db); returns false if this product must be issued on its own (group off / full / no weight gradient wanted)
+    // queue dw (+ db); returns false if this product must be issued on its own (group off / full / nothing wanted).
+    // A bias gradient whose weight gradient is NOT wanted is queued all the same, its dW going to scratch behind the group's slabs:
+    // the launch sums db slice by slice of its split, a stand-alone column sum in another order, and the bits of a requested
+    // gradient must not depend on which other destinations are NULL.
     bool add(const void* dy, int64_t ldy, const void* x, int64_t ldx, float* dw, float* db, int n_out, int k_in) {
-        if (!on || !dw || g.n >= 8 || (n_out % 8) || (k_in % 8) || (ldy % 8) || (ldx % 8)) return false;
+        if (!on || (!dw && !db) || g.n >= 8 || (n_out % 8) || (k_in % 8) || (ldy % 8) || (ldx % 8)) return false;
         mmae_dw_problem& q = g.p[g.n++];
         q.dy = dy; q.ldy = ldy; q.x = x; q.ldx = ldx; q.dw = dw; q.db = db; q.n_out = n_out; q.k_in = k_in;
+        if (!dw) scratch += (int64_t)n_out * k_in;
         return true;
     }
     int flush(const Ctx& c, hipStream_t st) {
         if (g.n == 0) return 0;
-        g.ws = c.ws_side; g.ws_elems = c.ws_side_elems;
-        if (mmae_gemm_dw_group_ws_elems(&g) > c.ws_side_elems) { mmae_set_error("composite: ws_side too small for the grouped weight gradients"); return MMAE_EINVAL; }
+        const int64_t need = mmae_gemm_dw_group_ws_elems(&g);       // a multiple of 8 floats (widths are): the scratch stays 16-byte aligned
+        if (need < 0 || need + scratch > c.ws_side_elems) { mmae_set_error("composite: ws_side too small for the grouped weight gradients"); return MMAE_EINVAL; }
+        float* sp = c.ws_side + need;                                // (with grad_acc the launch adds onto whatever the scratch holds: never read back)
+        for (int i = 0; i < g.n; ++i) if (!g.p[i].dw) { g.p[i].dw = sp; sp += (int64_t)g.p[i].n_out * g.p[i].k_in; }
+        g.ws = c.ws_side; g.ws_elems = need;
         const int rc = mmae_gemm_dw_group(&g, st);
-        g.n = 0;
+        g.n = 0; scratch = 0;
         return rc;
     }
 };
@@ -446,6 +454,10 @@ BlockTmp carve_block_tmp(Carver& cv, int B, int N, int D, int Hd, size_t es, boo
 }
 
 constexpr int NSET = 3;      // backward temporary sets of a stack (block l uses set l % NSET)
+// the most temporary sets any caller of run_blocks_bwd rotates through: a stack uses NSET, an adapter one per decoder block
+// (AdapterTmp::blocks, check_adapter: depth <= MAX_SETS).  run_blocks_bwd keeps one side-stream progress mark per set.
+constexpr int MAX_SETS = 8;
+static_assert(NSET <= MAX_SETS, "run_blocks_bwd keeps MAX_SETS side-stream progress marks");
 
 int64_t stack_mx_tmp_bytes(const mmae_stack_desc* d) {
     return 2 * mmae_mx_tmp_bytes(d->B * d->N, d->Hd > 3 * d->D ? d->Hd : 3 * d->D);
@@ -516,8 +528,9 @@ int run_blocks_bwd(const StackRun& s, int lo, int hi, const float* dx_top, const
     const float* dx = dx_top;
     const void* dx_act = dx_top_act;
     bool fc2_done = first_fc2_b_done;
-    hipEvent_t side_done[4] = {nullptr, nullptr, nullptr, nullptr};       // side_done[l % nset]: side work of block l enqueued
+    hipEvent_t side_done[MAX_SETS] = {};                                  // side_done[l % nset]: side work of block l enqueued
     int rc;
+    MMAE_REQUIRE(s.nset >= 1 && s.nset <= MAX_SETS, "stack_bwd: more temporary sets than side-stream progress marks");
     for (int l = hi - 1; l >= lo; --l) {
         BlockTmp t = s.tmps[l % s.nset];
         // Block l overwrites set l % nset.  The SIDE stream reads, for block k: its own set k % nset and its input gradient,
@@ -876,7 +889,7 @@ namespace {
 struct AdapterAct {
     float *ctx_tok, *te, *queries, *context, *qmean, *qrstd, *cmean, *crstd, *lse, *x, *omean, *orstd, *x1, *pat;
     void *enc_act, *qn, *cn, *q, *kv, *xo, *on, *hpre, *hact, *h_act;
-    BlockAct blocks[8];
+    BlockAct blocks[MAX_SETS];
     void* x3_tmp;
 };
 int kp_of(const mmae_adapter_desc* d) { return d->C * d->ph * d->pw; }
@@ -914,7 +927,7 @@ AdapterAct carve_adapter_act(Carver& cv, const mmae_adapter_desc* d) {
 struct AdapterTmp {
     void *d_pat, *dh_act, *d_hpre, *d_on, *dx_act, *d_xo, *d_q, *d_kv, *d_qn, *d_cn, *d_ctx_act;
     float *dh, *part_h, *dx, *part_o, *d_queries, *part_q, *d_context, *part_c, *d_ctx, *part_b;
-    BlockTmp blocks[8];
+    BlockTmp blocks[MAX_SETS];
     void* x3_tmp;
 };
 int64_t ldpat_of(const mmae_adapter_desc* d) { return (kp_of(d) + 7) / 8 * 8; }
@@ -946,7 +959,7 @@ AdapterTmp carve_adapter_tmp(Carver& cv, const mmae_adapter_desc* d) {
 int check_adapter(const mmae_adapter_desc* d) {
     MMAE_REQUIRE(d, "adapter: null descriptor");
     MMAE_REQUIRE(d->B > 0 && d->NC > 0 && d->Denc > 0 && d->D > 0 && d->heads > 0 && d->Hd > 0 && d->D % d->heads == 0 && d->depth >= 0 &&
-                 d->depth <= 8 && d->T >= 1 && d->T <= 7 && d->q_task >= -1 && d->q_task < d->T && d->G >= 0 && d->n_q > 0 && d->NC > d->G,
+                 d->depth <= MAX_SETS && d->T >= 1 && d->T <= 7 && d->q_task >= -1 && d->q_task < d->T && d->G >= 0 && d->n_q > 0 && d->NC > d->G,
                  "adapter: bad geometry");
     MMAE_REQUIRE(d->C > 0 && d->nh > 0 && d->nw > 0 && d->ph > 0 && d->pw > 0 && d->nh * d->nw == d->n_q, "adapter: bad patch geometry");
     MMAE_REQUIRE(d->act_dtype == MMAE_BF16 || d->act_dtype == MMAE_F16 || (d->act_dtype == MMAE_F32 && (d->f32_gemm == MMAE_F32X3 || d->f32_gemm == MMAE_F32F16)),
@@ -977,19 +990,19 @@ Ctx ctx_of(const mmae_adapter_desc* d, void* x3_tmp) {
 }  // namespace
 
 int64_t mmae_adapter_act_bytes(const mmae_adapter_desc* d) {
-    if (!d || d->depth < 0 || d->depth > 8) return 0;
+    if (!d || d->depth < 0 || d->depth > MAX_SETS) return 0;
     Carver cv(nullptr);
     (void)carve_adapter_act(cv, d);
     return cv.off;
 }
 int64_t mmae_adapter_tmp_bytes(const mmae_adapter_desc* d) {
-    if (!d || d->depth < 0 || d->depth > 8) return 0;
+    if (!d || d->depth < 0 || d->depth > MAX_SETS) return 0;
     Carver cv(nullptr);
     (void)carve_adapter_tmp(cv, d);
     return cv.off;
 }
 int64_t mmae_adapter_pat_offset(const mmae_adapter_desc* d) {
-    if (!d || d->depth < 0 || d->depth > 8) return -1;
+    if (!d || d->depth < 0 || d->depth > MAX_SETS) return -1;
     Carver cv(nullptr);
     AdapterAct a = carve_adapter_act(cv, d);
     return d->pat ? -1 : (int64_t)(uintptr_t)a.pat;       // caller-owned rows: not in the slab

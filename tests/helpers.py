@@ -211,6 +211,26 @@ class Guarded:
                                  f'first at {where}')
 
 
+def byte_slab(nbytes: int, device, guard: int = 64):
+    """A guarded slab of exactly nbytes bytes (a multiple of 4) for the library's byte-carved slabs: f32 elements, so that the guard
+    zones (64 elements = 256 bytes) keep the 256-byte alignment the carving assumes and start at the first byte past the slab."""
+    assert nbytes % 4 == 0 and nbytes > 0
+    return Guarded(1, nbytes // 4, nbytes // 4, torch.float32, device, guard=guard)
+
+
+def assert_untouched(g: 'Guarded', what: str):
+    """every element of a Guarded buffer allocated without `fill` -- the view included -- still holds the sentinel"""
+    n = int((g._bits() != _SENT[g.esz]).sum())
+    assert n == 0, f'{what}: {n} element(s) were written although the call was refused'
+
+
+def same_bits(a, b) -> bool:
+    """bit-for-bit equality of two tensors of one dtype and shape (NaN payloads and the sign of zero included)"""
+    assert a.dtype == b.dtype and a.shape == b.shape
+    it = _INT_OF[a.element_size()]
+    return bool(torch.equal(a.contiguous().view(it), b.contiguous().view(it)))
+
+
 def poisoned(X, ld: int, dtype, device, *, finite_to: int = 0, junk: float = 0.0, col0: int = 8, nan_rows: int = 8):
     """X [rows][cols] placed at column `col0` of a flat buffer with row stride ld (returns (flat, offset of X[0][0], ld)).  Columns
     cols .. finite_to hold `junk` (finite, the bytes a kernel may read past a ragged contraction edge: mmae.h's bf16 rule rounds
@@ -771,3 +791,281 @@ def mask_sample_ref(spt, task_noise, all_noise, offs, n_keep: int):
     restore = torch.empty_like(shuffle)
     restore.scatter_(1, shuffle, torch.arange(Ntot).expand(B, Ntot).contiguous())
     return (restore >= n_keep).long(), shuffle[:, :n_keep].contiguous(), restore
+
+
+# ----------------------------------------------------------------------------------------------
+# Stage references of a pre-LN transformer block (composite.hip: mmae_block_fwd / mmae_block_bwd), each in fp64 on the operands its
+# stage reads, with the element-wise bounds of the per-kernel checks: layernorm_ref restates the bound of
+# test_kernels_gpu._layernorm_per_element, linear_ref / linear_dx_ref / linear_dw_ref are prod_bound with the epilogue terms of
+# test_kernels_gpu._epilogues_per_element, the GELU pair carries that file's measured constants of the bf16 epilogues' polynomial.
+U_X3 = 2.0 ** -14                      # relative error of one split-bf16 product (MMAE_F32X3: hi hi + hi lo + lo hi, lo lo dropped)
+GELU_ABS, GELU_REL, DGELU_ABS = 1.3e-4, 2.6e-5, 5.5e-4      # DESIGN.md section 6 item 12 (tools/gelu_poly_fit.py)
+GELU_D1, GELU_D2 = 1.13, 0.8           # max |gelu'|, max |gelu''|: how a pre-activation error propagates
+
+
+def gelu_ref(z):
+    """(gelu(z), gelu'(z)) in fp64, the erf form"""
+    z = z.double()
+    Phi = 0.5 * (1 + torch.erf(z / math.sqrt(2)))
+    phi = torch.exp(-0.5 * z * z) / math.sqrt(2 * math.pi)
+    return z * Phi, Phi + z * phi
+
+
+class layernorm_ref:
+    """LayerNorm over the last dimension of x [R, D] (f32 values) in fp64 with the kernels' bounds (u = 2^-24, fp32 arithmetic):
+      mean    |dm| <= gamma_D mean|x| + ulp
+      rstd    relative rho <= gamma_(2D+4) mean(x^2) / var / 2 + 2^-21     (one- or two-pass variance, halved by the root; rsq within 1 ulp)
+      xhat    |dxh| <= |xh| (rho + 2u) + rstd |dm|
+      y       |dy_| <= |w| |dxh| + 4u (|xh w| + |b|) + ulp(out)
+    bwd(dy, dx_in): dx = dx_in + rstd (g - mean g - xh mean(g xh)), g = dy w, with
+      |ddx| <= rho |dx - dx_in| + rstd (gamma_D mean|g| + |dxh| mean|g xh| + |xh| mean(|g| |dxh|) + gamma_D |xh| mean|g xh|)
+               + 6u (|dx_in| + rstd (|g| + mean|g| + |xh| mean|g xh|)) + ulp_f32
+    and the parameter gradients dgamma = sum_r dy xh, dbeta = sum_r dy over R rows in `extra` more partial sums:
+      the rows' bounds summed + gamma_(R + extra) sum of magnitudes."""
+
+    def __init__(self, x, w, b, eps: float):
+        u = U32
+        self.x, self.w, self.b = x.double(), w.double(), b.double()
+        self.R, self.D = self.x.shape
+        D = self.D
+        self.mean = self.x.mean(1)
+        xc = self.x - self.mean[:, None]
+        self.var = (xc * xc).mean(1)
+        self.rstd = 1.0 / torch.sqrt(self.var + float(_h(eps, 'cpu')))
+        self.xh = xc * self.rstd[:, None]
+        self.b_mean = gamma(D) * self.x.abs().mean(1) + ulp(torch.float32, self.mean)
+        self.rho = gamma(2 * D + 4) * (self.x * self.x).mean(1) / (self.var + float(_h(eps, 'cpu'))) / 2 + 2.0 ** -21
+        self.b_rstd = self.rho * self.rstd + ulp(torch.float32, self.rstd)
+        self.e_xh = self.xh.abs() * (self.rho[:, None] + 2 * u) + self.rstd[:, None] * self.b_mean[:, None]
+        self.y = self.xh * self.w + self.b
+        self._b_y = self.w.abs() * self.e_xh + 4 * u * ((self.xh * self.w).abs() + self.b.abs())
+
+    def b_y(self, out_dtype):
+        return self._b_y + ulp(out_dtype, self.y.abs() + self._b_y)
+
+    def bwd(self, dy, dx_in=None, act_dtype=None, extra: int = 0):
+        """returns dict: dx (ref, bound f32[, bound in act_dtype]), dgamma (ref, bound), dbeta (ref, bound)"""
+        u, D, R = U32, self.D, self.R
+        dy = dy.double()
+        dx_in = torch.zeros_like(dy) if dx_in is None else dx_in.double()
+        rs, xh, e_xh = self.rstd[:, None], self.xh, self.e_xh
+        g = dy * self.w
+        mg = g.abs().mean(1, keepdim=True)
+        gx = (g * xh).mean(1, keepdim=True)
+        agx = (g * xh).abs().mean(1, keepdim=True)
+        ref = dx_in + rs * (g - g.mean(1, keepdim=True) - xh * gx)
+        bd = (self.rho[:, None] * (ref - dx_in).abs()
+              + rs * (gamma(D) * mg + e_xh * agx + xh.abs() * (g.abs() * e_xh).mean(1, keepdim=True) + gamma(D) * xh.abs() * agx)
+              + 6 * u * (dx_in.abs() + rs * (g.abs() + mg + xh.abs() * agx)))
+        b32 = bd + ulp(torch.float32, ref.abs() + bd)
+        out = dict(dx=(ref, b32), dx_act=None)
+        if act_dtype is not None:
+            out['dx_act'] = (ref, b32 + ulp(act_dtype, ref.abs() + b32))
+        dg = (dy * xh).sum(0)
+        out['dgamma'] = (dg, (dy.abs() * e_xh).sum(0) + gamma(R + 1 + extra) * (dy * xh).abs().sum(0))
+        out['dbeta'] = (dy.sum(0), gamma(R + extra) * dy.abs().sum(0) + 0 * dg)
+        return out
+
+
+def linear_ref(x, w, bias=None, resid=None, out_dtype=torch.float32, u_op: float = 0.0, k_mult: int = 1):
+    """y = x w^T (+ bias) (+ resid) in fp64 on the operands as stored ([M, K], [N, K]) and its bound: prod_bound's product term over
+    k_mult K accumulated terms (3 K when a split-bf16 product runs as one bf16 product over [hi | lo | hi]), one fp32 rounding per
+    epilogue addition (2u |y| for the bias, 2u more for the residual), the final rounding into out_dtype.
+    Returns (y, bound, pre) -- pre = (x w^T + bias, its bound before the final rounding), what an activation epilogue starts from."""
+    x, w = x.double(), w.double()
+    K = x.shape[1]
+    lin = x @ w.t()
+    if bias is not None:
+        lin = lin + bias.double()
+    e = prod_bound(x.abs(), w.abs(), k_mult * K, u_op=u_op) + 2 * U32 * lin.abs()
+    y = lin
+    b = e
+    if resid is not None:
+        y = lin + resid.double()
+        b = e + 2 * U32 * y.abs()
+    return y, b + ulp(out_dtype, y.abs() + b), (lin, e)
+
+
+def linear_dx_ref(dy, w, out_dtype, u_op: float = 0.0, k_mult: int = 1, mul=None, dgelu_of=None):
+    """dx = dy w (dy [M, N], w [N, K]) in fp64, optionally times `mul` (MMAE_EPI_MUL: a stored derivative) or times gelu'(dgelu_of)
+    (MMAE_EPI_DGELU: re-evaluated from the stored pre-activation), with the bounds of test_kernels_gpu._epilogues_per_element.
+    Returns (ref, bound incl. the rounding into out_dtype, bound before that rounding -- what the epilogue's column sums add up)."""
+    dy, w = dy.double(), w.double()
+    N = dy.shape[1]
+    g = dy @ w
+    Eg = prod_bound(dy.abs(), w.t().abs(), k_mult * N, u_op=u_op)
+    if mul is not None:
+        r = g * mul.double()
+        b = Eg * mul.double().abs() + 2 * U32 * r.abs()
+    elif dgelu_of is not None:
+        r = g * gelu_ref(dgelu_of)[1]
+        b = GELU_D1 * Eg + g.abs() * DGELU_ABS + 2 * U32 * r.abs()
+    else:
+        r, b = g, Eg
+    return r, b + ulp(out_dtype, r.abs() + b), b
+
+
+def linear_dw_ref(dy, x, u_op: float = 0.0, g0=None):
+    """dw = dy^T x ([M, N], [M, K] -> [N, K]) and db = colsum(dy) in fp64 over the M rows, f32 destinations; g0 = (dw0, db0): added
+    onto these (grad_acc: one more term in gamma).  Returns (dw, bound), (db, bound)."""
+    dy, x = dy.double(), x.double()
+    M = dy.shape[0]
+    t = 0 if g0 is None else 1
+    dw = dy.t() @ x
+    db = dy.sum(0)
+    aw, ab = dy.t().abs() @ x.abs(), dy.abs().sum(0)
+    if g0 is not None:
+        dw, db = dw + g0[0].double(), db + g0[1].double()
+        aw, ab = aw + g0[0].double().abs(), ab + g0[1].double().abs()
+    bw = (gamma(M + t) + u_op) * aw
+    bb = gamma(M + t) * ab
+    return (dw, bw + ulp(torch.float32, dw.abs() + bw)), (db, bb + ulp(torch.float32, db.abs() + bb))
+
+
+def colsum_ref(x, terms: int = 0, g0=None):
+    """fp64 column sums of x [M, n] as stored and the bound of ANY fp32 summation tree over its M (+ terms more partial sums, + 1 when
+    added onto g0) terms: gamma times the column sums of the magnitudes."""
+    x = x.double()
+    s, a = x.sum(0), x.abs().sum(0)
+    n = x.shape[0] + terms
+    if g0 is not None:
+        s, a, n = s + g0.double(), a + g0.double().abs(), n + 1
+    return s, gamma(n) * a
+
+
+def heads_of(t, B, N, H, hd, col0: int = 0):
+    """[B * N][ld] rows, head h at columns col0 + h * hd -> [B * H][N][hd]"""
+    return t[:, col0:col0 + H * hd].reshape(B, N, H, hd).permute(0, 2, 1, 3).reshape(B * H, N, hd)
+
+
+def rows_of(t, B, N, H, hd):
+    """inverse of heads_of: [B * H][N][hd] -> [B * N][H * hd]"""
+    return t.reshape(B, H, N, hd).permute(0, 2, 1, 3).reshape(B * N, H * hd)
+
+
+def block_ref(x0, P, heads: int, eps: float, B: int, N: int, dy=None, dp1=None, dp2=None):
+    """One pre-LN block composed from the stage references above (layernorm_ref, linear_ref, attention_bounds, gelu_ref), every stage
+    fed with the previous stage's fp64 result: x1 = x0 + dp1 attn(norm1(x0)), x2 = x1 + dp2 mlp(norm2(x1)); with dy = d(x2) also the
+    backward.  P: the 12 parameters in the order n1_w n1_b qkv_w qkv_b proj_w proj_b n2_w n2_b fc1_w fc1_b fc2_w fc2_b; dp1 / dp2:
+    per-sample scales [B] or None.  Returns a dict of every stage's reference (bounds dropped: this is what
+    tests/test_check_helpers_cpu.py holds against torch autograd of a plainly written block)."""
+    n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = (t.double() for t in P)
+    R, D = x0.shape
+    hd = D // heads
+    sc = hd ** -0.5
+    row = lambda s: torch.ones(R, 1, dtype=torch.float64, device=x0.device) if s is None else s.double().repeat_interleave(N)[:, None]
+    s1, s2 = row(dp1), row(dp2)
+    o = {}
+    l1 = layernorm_ref(x0, n1w, n1b, eps)
+    o['ln1'] = l1.y
+    o['qkv'] = linear_ref(o['ln1'], qkvw, qkvb)[0]
+    hv = lambda c: heads_of(o['qkv'], B, N, heads, hd, c)
+    s = sc * (hv(0) @ hv(D).transpose(-1, -2))
+    o['lse'] = torch.logsumexp(s, -1)
+    o['ao'] = rows_of(torch.exp(s - o['lse'][..., None]) @ hv(2 * D), B, N, heads, hd)
+    o['x1'] = x0.double() + s1 * linear_ref(o['ao'], projw, projb)[0]
+    l2 = layernorm_ref(o['x1'], n2w, n2b, eps)
+    o['ln2'] = l2.y
+    o['pre'] = linear_ref(o['ln2'], fc1w, fc1b)[0]
+    o['hact'], o['dgelu'] = gelu_ref(o['pre'])
+    o['x2'] = o['x1'] + s2 * linear_ref(o['hact'], fc2w, fc2b)[0]
+    if dy is None:
+        return o
+    dy = dy.double()
+    dm = dy * s2
+    (o['g_fc2_w'], _), (o['g_fc2_b'], _) = linear_dw_ref(dm, o['hact'])
+    o['d_hpre'] = linear_dx_ref(dm, fc2w, torch.float32, mul=o['dgelu'])[0]
+    (o['g_fc1_w'], _), (o['g_fc1_b'], _) = linear_dw_ref(o['d_hpre'], o['ln2'])
+    o['d_ln2'] = linear_dx_ref(o['d_hpre'], fc1w, torch.float32)[0]
+    b2 = l2.bwd(o['d_ln2'], dy)
+    o['dx1'], o['g_n2_w'], o['g_n2_b'] = b2['dx'][0], b2['dgamma'][0], b2['dbeta'][0]
+    da = o['dx1'] * s1
+    (o['g_proj_w'], _), (o['g_proj_b'], _) = linear_dw_ref(da, o['ao'])
+    o['d_ao'] = linear_dx_ref(da, projw, torch.float32)[0]
+    ab = attention_bounds(hv(0), hv(D), hv(2 * D), heads_of(o['d_ao'], B, N, heads, hd), sc, u_in=0.0, u_p=0.0, out_dtype=torch.float32)
+    o['d_qkv'] = torch.cat([rows_of(ab[k][0], B, N, heads, hd) for k in ('dq', 'dk', 'dv')], 1)
+    (o['g_qkv_w'], _), (o['g_qkv_b'], _) = linear_dw_ref(o['d_qkv'], o['ln1'])
+    o['d_ln1'] = linear_dx_ref(o['d_qkv'], qkvw, torch.float32)[0]
+    b1 = l1.bwd(o['d_ln1'], o['dx1'])
+    o['dx0'], o['g_n1_w'], o['g_n1_b'] = b1['dx'][0], b1['dgamma'][0], b1['dbeta'][0]
+    o['g_cs'] = colsum_ref(o['dx0'])[0]
+    return o
+
+
+# ----------------------------------------------------------------------------------------------
+# The whole SpatialOutputAdapter in fp64, restated from mmae.h's description of mmae_adapter_desc and mmae_decoder_build (not from the
+# oracle): the yardstick the per-kernel path's error is MEASURED against, and the composite's held to (tests/test_composite_gpu.py).
+def plain_block(x, P, heads: int, eps: float, B: int, N: int):
+    """a pre-LN block written out plainly in torch (any float dtype, differentiable): x [B * N, D], P the 12 parameters"""
+    n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = P
+    D = x.shape[1]
+    hd = D // heads
+    F = torch.nn.functional
+    qkv = F.linear(F.layer_norm(x, (D,), n1w, n1b, eps), qkvw, qkvb).reshape(B, N, 3, heads, hd).permute(2, 0, 3, 1, 4)
+    a = ((qkv[0] @ qkv[1].transpose(-1, -2)) * hd ** -0.5).softmax(-1) @ qkv[2]
+    x1 = x + F.linear(a.transpose(1, 2).reshape(B * N, D), projw, projb)
+    h = F.linear(F.layer_norm(x1, (D,), n2w, n2b, eps), fc1w, fc1b)
+    return x1 + F.linear(h * 0.5 * (1 + torch.erf(h / math.sqrt(2))), fc2w, fc2b)
+
+
+def decoder_rows_ref(ctx, ids_keep, ids_restore, mask_token, temb, pos, offs, q_task: int, G: int, n_q: int):
+    """mmae_decoder_build's formulae: ctx [B, n_keep + G, D] -> (queries [B, n_q, D], context [B, n_keep + G, D]).
+      q[b][j] = (ids_restore[b][off(q_task) + j] < n_keep ? ctx[b][that rank] : mask_token) + task_emb[q_task] + pos[j]
+      q_task = -1: q[b][j] = mask_token + pos[j]
+      c[b][r] = ctx[b][r] + task_emb[task(ids_keep[b][r])] + pos[ids_keep[b][r] - off(task)] for r < n_keep; global rows copied
+    temb: list of [D] tensors or None (= zeros)."""
+    B, NC, D = ctx.shape
+    n_keep = NC - G
+    te = torch.stack([torch.zeros(D, dtype=ctx.dtype, device=ctx.device) if t is None else t for t in temb])
+    if q_task < 0:
+        q = (mask_token + pos)[None].expand(B, n_q, D)
+    else:
+        rank = ids_restore[:, offs[q_task]:offs[q_task] + n_q]
+        vis = rank < n_keep
+        got = torch.gather(ctx, 1, rank.clamp_max(NC - 1)[..., None].expand(B, n_q, D))
+        q = torch.where(vis[..., None], got, mask_token.expand(B, n_q, D)) + te[q_task] + pos
+    task = token_owner(ids_keep, offs)
+    off_t = torch.as_tensor(list(offs), device=ids_keep.device)[task]
+    c = ctx[:, :n_keep] + te[task] + pos[ids_keep - off_t]
+    return q, torch.cat([c, ctx[:, n_keep:]], 1)
+
+
+def adapter_ref(enc, ids_keep, ids_restore, params, *, T, q_task, G, D, heads, depth, pos, offs, C, nh, nw, ph, pw, eps, d_img=None):
+    """SpatialOutputAdapter.forward in fp64 from its parameters (SpatialAdapterFn's order: mask_token, task_emb[0..T-1] (None = none),
+    q.w q.b kv.w kv.b proj.w proj.b ctxn.w ctxn.b qn.w qn.b outn.w outn.b fc1.w fc1.b fc2.w fc2.b, 12 per block, out_proj.w out_proj.b,
+    proj_context.w proj_context.b; weights as the products read them): proj_context, the query / context rows, cross-attention
+    (queries over the context, no residual around it), x + mlp(out_norm(x)), the blocks, out_proj, patch rows -> image.  With d_img
+    also the backward, by autograd of exactly this forward.  Returns (img, pat) or (img, pat, d_enc, [gradient per parameter or None])."""
+    F = torch.nn.functional
+    ps = [None if p is None else p.detach().double().clone().requires_grad_(d_img is not None) for p in params]
+    enc = enc.detach().double().clone().requires_grad_(d_img is not None)
+    mask, temb = ps[0], ps[1:1 + T]
+    qw, qb, kvw, kvb, pw_, pb, cnw, cnb, qnw, qnb, onw, onb, f1w, f1b, f2w, f2b = ps[1 + T:17 + T]
+    blocks = ps[17 + T:17 + T + 12 * depth]
+    ow, ob, pcw, pcb = ps[17 + T + 12 * depth:]
+    B, NC, _ = enc.shape
+    n_q, hd = nh * nw, D // heads
+    ctx = F.linear(enc, pcw, pcb)
+    q_rows, c_rows = decoder_rows_ref(ctx, ids_keep, ids_restore, mask.reshape(D), [None if t is None else t.reshape(D) for t in temb],
+                                      pos.double(), offs, q_task, G, n_q)
+    qn, cn = F.layer_norm(q_rows, (D,), qnw, qnb, eps), F.layer_norm(c_rows, (D,), cnw, cnb, eps)
+    q = F.linear(qn, qw, qb).reshape(B, n_q, heads, hd).transpose(1, 2)
+    kv = F.linear(cn, kvw, kvb).reshape(B, NC, 2, heads, hd).permute(2, 0, 3, 1, 4)
+    xo = (((q @ kv[0].transpose(-1, -2)) * hd ** -0.5).softmax(-1) @ kv[1]).transpose(1, 2).reshape(B * n_q, D)
+    x = F.linear(xo, pw_, pb)
+    h = F.linear(F.layer_norm(x, (D,), onw, onb, eps), f1w, f1b)
+    x = x + F.linear(h * 0.5 * (1 + torch.erf(h / math.sqrt(2))), f2w, f2b)
+    for l in range(depth):
+        x = plain_block(x, blocks[12 * l:12 * l + 12], heads, eps, B, n_q)
+    pat = F.linear(x, ow, ob)
+    img = _rows_img_rect(pat.reshape(B, n_q, C * ph * pw), C, nh, nw, ph, pw)
+    if d_img is None:
+        return img.detach(), pat.detach()
+    img.backward(d_img.double())
+    return img.detach(), pat.detach(), enc.grad, [None if p is None else p.grad for p in ps]
+
+
+def _rows_img_rect(r, C, nh, nw, ph, pw):
+    """[B, nh * nw, C * ph * pw] patch rows (column order c, i, j) -> [B, C, nh * ph, nw * pw]"""
+    B = r.shape[0]
+    return r.reshape(B, nh, nw, C, ph, pw).permute(0, 3, 1, 4, 2, 5).reshape(B, C, nh * ph, nw * pw)

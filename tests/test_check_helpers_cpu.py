@@ -662,3 +662,182 @@ def test_guarded_int64_buffer_flags_a_write_into_one_guard_element():
     gb2.flat[gb2.off - 1] = 3
     with pytest.raises(AssertionError, match='guard zone before'):
         gb2.intact()
+
+
+# ----------------------------------------------------------------------------------------------
+# The stage references of a transformer block (tests/test_composite_gpu.py composes them against mmae_block_fwd / mmae_block_bwd)
+def _plain_block(x, P, heads, eps, B, N, dp1=None, dp2=None):
+    """a pre-LN block written out plainly in torch (fp64 autograd is the reference of block_ref)"""
+    n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = P
+    D = x.shape[1]
+    hd = D // heads
+    F = torch.nn.functional
+    row = lambda s: 1.0 if s is None else s.double().repeat_interleave(N)[:, None]
+    qkv = F.linear(F.layer_norm(x, (D,), n1w, n1b, eps), qkvw, qkvb).reshape(B, N, 3, heads, hd).permute(2, 0, 3, 1, 4)
+    a = ((qkv[0] @ qkv[1].transpose(-1, -2)) * hd ** -0.5).softmax(-1) @ qkv[2]
+    x1 = x + row(dp1) * F.linear(a.transpose(1, 2).reshape(B * N, D), projw, projb)
+    h = F.linear(F.layer_norm(x1, (D,), n2w, n2b, eps), fc1w, fc1b)
+    return x1 + row(dp2) * F.linear(h * 0.5 * (1 + torch.erf(h / math.sqrt(2))), fc2w, fc2b), x1
+
+
+def _block_params(D, Hd, g):
+    shapes = [(D,), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (D,), (D,), (Hd, D), (Hd,), (D, Hd), (D,)]
+    return [(torch.randn(s, generator=g) * (0.1 if len(s) == 2 else 0.2) + (1.0 if i in (0, 6) else 0.0)).double() for i, s in enumerate(shapes)]
+
+
+@pytest.mark.parametrize('dp', [False, True])
+def test_block_stage_references_compose_to_autograd_of_a_plain_block(dp):
+    from helpers import block_ref
+    g = torch.Generator().manual_seed(5)
+    B, N, D, heads, Hd = 2, 7, 16, 2, 24
+    P = [p.requires_grad_(True) for p in _block_params(D, Hd, g)]
+    x = (torch.randn(B * N, D, generator=g) + 0.3).double().requires_grad_(True)
+    dy = torch.randn(B * N, D, generator=g).double()
+    dp1 = torch.tensor([0.0, 1.25]) if dp else None
+    dp2 = torch.tensor([2.0, 0.0]) if dp else None
+    y, x1 = _plain_block(x, P, heads, 1e-6, B, N, dp1, dp2)
+    y.backward(dy)
+    o = block_ref(x.detach(), [p.detach() for p in P], heads, 1e-6, B, N, dy=dy, dp1=dp1, dp2=dp2)
+    close = lambda a, b, what: torch.testing.assert_close(a, b, rtol=1e-10, atol=1e-12, msg=lambda m: f'{what}: {m}')
+    close(o['x1'], x1.detach(), 'x1')
+    close(o['x2'], y.detach(), 'x2')
+    close(o['dx0'], x.grad, 'dx0')
+    names = ['g_n1_w', 'g_n1_b', 'g_qkv_w', 'g_qkv_b', 'g_proj_w', 'g_proj_b', 'g_n2_w', 'g_n2_b', 'g_fc1_w', 'g_fc1_b', 'g_fc2_w', 'g_fc2_b']
+    for n, p in zip(names, P):
+        close(o[n], p.grad, n)
+    close(o['g_cs'], x.grad.sum(0), 'g_cs')
+    if dp:                                             # a dropped sample: its rows pass through, its branch gets no gradient
+        assert torch.equal(o['x1'][:N], x.detach()[:N]) and torch.equal(o['x2'][N:], o['x1'][N:])
+        assert not o['d_hpre'][N:].any() and not o['d_ao'][:N].any()
+
+
+def test_layernorm_ref_bounds_hold_for_an_fp32_evaluation_and_flag_a_stale_statistic():
+    from helpers import layernorm_ref
+    g = torch.Generator().manual_seed(6)
+    R, D = 100, 128
+    x = torch.randn(R, D, generator=g) * 2 + 0.5
+    w, b, dy, dxin = torch.randn(D, generator=g), torch.randn(D, generator=g), torch.randn(R, D, generator=g), torch.randn(R, D, generator=g)
+    ln = layernorm_ref(x, w, b, 1e-6)
+    xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    y = torch.nn.functional.layer_norm(xr, (D,), wr, br, 1e-6)          # an fp32 evaluation: inside the bounds
+    y.backward(dy)
+    assert_within(y, ln.y, ln.b_y(torch.float32), 'y f32')
+    assert_within(y.bfloat16(), ln.y, ln.b_y(torch.bfloat16), 'y bf16')
+    r = ln.bwd(dy, dxin, torch.bfloat16)
+    assert_within(xr.grad + dxin, *r['dx'], 'dx')
+    assert_within((xr.grad + dxin).bfloat16(), *r['dx_act'], 'dx bf16')
+    assert_within(wr.grad, *r['dgamma'], 'dgamma')
+    assert_within(br.grad, *r['dbeta'], 'dbeta')
+    stale = y.detach().clone()
+    stale[17] = (x[17] - x[16].mean()) * float(ln.rstd[17]) * w + b      # row 17 normalised with row 16's mean
+    with pytest.raises(AssertionError, match='row=17|\\(17,'):
+        assert_within(stale, ln.y, ln.b_y(torch.float32), 'y', names=('row', 'col'))
+
+
+def test_linear_and_colsum_references_pass_the_rounded_exact_result_and_flag_one_wrong_bias_entry():
+    from helpers import colsum_ref, gelu_ref, linear_dw_ref, linear_dx_ref, linear_ref
+    g = torch.Generator().manual_seed(7)
+    M, N, K = 100, 48, 128
+    x, w = torch.randn(M, K, generator=g).bfloat16(), (torch.randn(N, K, generator=g) * 0.1).bfloat16()
+    bias, resid = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
+    y, by, (lin, e) = linear_ref(x, w, bias, resid)
+    assert_within(y.float(), y, by, 'linear f32')
+    y16, by16, _ = linear_ref(x, w, bias, out_dtype=torch.bfloat16)
+    assert_within(y16.bfloat16(), y16, by16, 'linear bf16')
+    bad = y.float().clone()
+    bad[:, 5] += 4 * float(by[:, 5].max())
+    with pytest.raises(AssertionError):
+        assert_within(bad, y, by, 'linear, one bias entry off')
+    dy = torch.randn(M, N, generator=g).bfloat16()
+    pre = torch.randn(M, K, generator=g).bfloat16()
+    r, b, _ = linear_dx_ref(dy, w, torch.bfloat16, dgelu_of=pre)
+    assert_within(r.bfloat16(), r, b, 'dgelu')
+    r2, b2, _ = linear_dx_ref(dy, w, torch.bfloat16, mul=gelu_ref(pre)[1])
+    assert torch.equal(r, r2)
+    (dw, bw), (db, bb) = linear_dw_ref(dy, x)
+    assert_within(dw.float(), dw, bw, 'dw')
+    assert_within(db.float(), db, bb, 'db')
+    g0 = (torch.randn(N, K, generator=g), torch.randn(N, generator=g))
+    (dwa, bwa), (dba, bba) = linear_dw_ref(dy, x, g0=g0)
+    assert torch.equal(dwa, dw + g0[0].double()) and bool((bwa >= bw).all()) and bool((bba >= bb).all())
+    s, bs = colsum_ref(dy)
+    assert_within(dy.float().sum(0), s, bs, 'column sums in fp32')
+    wrong = s.float().clone()
+    wrong[3] = float(dy.float()[:-1, 3].sum())          # one row missing from one column
+    with pytest.raises(AssertionError):
+        assert_within(wrong, s, bs, 'column sums, one row short')
+
+
+def _tiny_adapter(depth, q_task, seed=3):
+    g = torch.Generator().manual_seed(seed)
+    B, T, nh, nw, n_keep, G, Denc, D, heads, Hd, C, ph, pw = 2, 3, 2, 3, 5, 1, 8, 8, 2, 12, 2, 2, 2
+    n_q, KP = nh * nw, C * ph * pw
+    rn = lambda *s: torch.randn(*s, generator=g).double() * 0.4
+    lin = lambda n, k: [rn(n, k), rn(n)]
+    ln = lambda: [1 + rn(D), rn(D)]
+    params = [rn(D), rn(D), None, rn(D)] + lin(D, D) + lin(2 * D, D) + lin(D, D) + ln() + ln() + ln() + lin(Hd, D) + lin(D, Hd)
+    for _ in range(depth):
+        params += ln() + lin(3 * D, D) + lin(D, D) + ln() + lin(Hd, D) + lin(D, Hd)
+    params += lin(KP, D) + lin(D, Denc)
+    perm = torch.stack([torch.randperm(T * n_q, generator=g) for _ in range(B)])
+    kw = dict(T=T, q_task=q_task, G=G, D=D, heads=heads, depth=depth, pos=rn(n_q, D), offs=[0, n_q, 2 * n_q, 3 * n_q], C=C, nh=nh, nw=nw, ph=ph,
+              pw=pw, eps=1e-6)
+    return rn(B, n_keep + G, Denc), perm[:, :n_keep].contiguous(), torch.argsort(perm, 1), params, kw
+
+
+@pytest.mark.parametrize('q_task', [-1, 1])
+def test_decoder_rows_ref_against_the_formulae_written_as_loops(q_task):
+    from helpers import decoder_rows_ref
+    g = torch.Generator().manual_seed(4)
+    B, T, n_q, n_keep, G, D = 2, 3, 6, 5, 1, 4
+    offs = [0, 6, 12, 18]
+    ctx, mask, pos = torch.randn(B, n_keep + G, D, generator=g).double(), torch.randn(D, generator=g).double(), torch.randn(n_q, D, generator=g).double()
+    temb = [torch.randn(D, generator=g).double(), None, torch.randn(D, generator=g).double()]
+    perm = torch.stack([torch.randperm(T * n_q, generator=g) for _ in range(B)])
+    keep, restore = perm[:, :n_keep].contiguous(), torch.argsort(perm, 1)
+    q, c = decoder_rows_ref(ctx, keep, restore, mask, temb, pos, offs, q_task, G, n_q)
+    te = lambda t: 0 if temb[t] is None else temb[t]
+    for b in range(B):
+        for j in range(n_q):
+            if q_task < 0:
+                want = mask + pos[j]
+            else:
+                r = int(restore[b, offs[q_task] + j])
+                want = (ctx[b, r] if r < n_keep else mask) + te(q_task) + pos[j]
+            assert torch.equal(q[b, j], want)
+        for r in range(n_keep):
+            t = int(keep[b, r]) // n_q
+            assert torch.equal(c[b, r], ctx[b, r] + te(t) + pos[int(keep[b, r]) - offs[t]])
+        assert torch.equal(c[b, n_keep:], ctx[b, n_keep:])
+    if q_task >= 0:                                   # every kept token of the query task is looked up at its own rank
+        assert any(int(restore[b, offs[q_task] + j]) < n_keep for b in range(B) for j in range(n_q))
+
+
+def test_adapter_ref_blocks_are_block_ref_and_its_gradients_match_finite_differences():
+    from helpers import adapter_ref, block_ref, plain_block
+    g = torch.Generator().manual_seed(8)
+    P = _block_params(16, 24, g)
+    x = torch.randn(14, 16, generator=g).double()
+    torch.testing.assert_close(plain_block(x, P, 2, 1e-6, 2, 7), block_ref(x, P, 2, 1e-6, 2, 7)['x2'], rtol=1e-10, atol=1e-12)
+    enc, keep, restore, params, kw = _tiny_adapter(depth=1, q_task=1)
+    d_img = torch.randn(2, 2, 4, 6, generator=g).double()
+    img, pat, d_enc, grads = adapter_ref(enc, keep, restore, params, d_img=d_img, **kw)
+    assert grads[2] is None and img.shape == (2, 2, 4, 6)
+    loss = lambda e, ps: float((adapter_ref(e, keep, restore, ps, **kw)[0] * d_img).sum())
+    h = 1e-6
+
+    def fd(bump):                                      # central difference of <img, d_img> along one coordinate
+        return (loss(*bump(+h)) - loss(*bump(-h))) / (2 * h)
+    for idx in [(0, 0, 0), (1, 3, 5), (1, 5, 7)]:      # a kept token of each sample, the global token
+        def bump(s, idx=idx):
+            e = enc.clone()
+            e[idx] += s
+            return e, params
+        assert fd(bump) == pytest.approx(float(d_enc[idx]), rel=1e-5, abs=1e-8)
+    for i in (0, 1, 4, 9, 17, 20, len(params) - 4, len(params) - 1):      # mask token, a task embedding, q.w, ctxn.b, fc1.w, block n1.b, out_proj.w, pc.b
+        flat = 1 if params[i].numel() > 1 else 0
+        def bump(s, i=i, flat=flat):
+            ps = [None if p is None else p.clone() for p in params]
+            ps[i].view(-1)[flat] += s
+            return enc, ps
+        assert fd(bump) == pytest.approx(float(grads[i].reshape(-1)[flat]), rel=1e-5, abs=1e-8), i
