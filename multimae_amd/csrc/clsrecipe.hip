@@ -90,20 +90,13 @@ __global__ void __launch_bounds__(256) mix_target_kernel(const long long* __rest
 
 // ---- soft-target cross-entropy ------------------------------------------------------------------------------------------------------
 // fixed-order sums / maxima over the 256 threads of a workgroup: xor-shuffle tree inside a wave, the four waves in wave order
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-    v = wave_sum(v);
+__device__ __forceinline__ void put_wave(float v, float* sh) {
     __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
-__device__ __forceinline__ float block_max(float v, float* sh) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
+__device__ __forceinline__ float block_sum(float v, float* sh) { put_wave(wave_sum(v), sh); return join4_sum(sh); }
+__device__ __forceinline__ float block_max(float v, float* sh) { put_wave(wave_max(v), sh); return join4_max(sh); }
 
 // the target of element k of a row: the dense row, or smoothing / K + (1 - smoothing) [k == label]
 struct Tgt {
@@ -161,13 +154,8 @@ __global__ void __launch_bounds__(256) soft_ce_finish_kernel(const float* __rest
     __shared__ double s[256];
     double a = 0.0;
     for (int i = threadIdx.x; i < B; i += 256) a += (double)rowloss[i];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)(s[0] / (double)B);
+    a = block_tree_sum(a, s);
+    if (threadIdx.x == 0) out[0] = (float)(a / (double)B);
 }
 
 // dx[b][k] = (up / B) (exp(x_k - lse_b) tsum_b - t_k) for k < K, 0 for K <= k < ldx; one workgroup per row

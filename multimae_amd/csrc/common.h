@@ -228,6 +228,27 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// the four waves' values of a 256-thread workgroup (sh[wave]) joined in wave order
+__device__ __forceinline__ float join4_sum(const float* sh) { return ((sh[0] + sh[1]) + sh[2]) + sh[3]; }
+__device__ __forceinline__ float join4_max(const float* sh) { return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])); }
+// a fixed tree over the 256 threads' values (each usually a strided pre-sum) through the LDS array s[256]: 128 .. 1; every thread
+// must call and gets the result; s is not to be written again before a barrier
+template <class T, class Op>
+__device__ __forceinline__ T block_tree(T v, T* s, Op op) {
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s[threadIdx.x] = op(s[threadIdx.x], s[threadIdx.x + o]);
+        __syncthreads();
+    }
+    return s[0];
+}
+__device__ __forceinline__ double block_tree_sum(double v, double* s) {
+    return block_tree(v, s, [](double a, double b) { return a + b; });
+}
+__device__ __forceinline__ float block_tree_max(float v, float* s) {
+    return block_tree(v, s, [](float a, float b) { return fmaxf(a, b); });
+}
 
 // ---- the bilinear resize's four-tap combination (csrc/convnext.hip resize_fwd_kernel; csrc/regloss.hip) -------------------------
 // ly0 (lx0 a + lx1 b) + ly1 (lx0 c + lx1 d) for the taps a, b (row i0 at columns i0, i1) and c, d (row i1), with every rounding

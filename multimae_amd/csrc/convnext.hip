@@ -9,8 +9,9 @@
 //     caller sums them in a fixed order with mmae_colsum_partials);
 //   - the final F.interpolate (output_adapters.py:568) from the low-resolution NHWC logits to the full-resolution NCHW output,
 //     bilinear or nearest with PyTorch's source-index formulas (align_corners=False, scale = in / out), and its backward as a
-//     gather: every low-resolution element sums its own output window in a fixed order.
-#include "common.h"
+//     gather: every low-resolution element sums its own output window in a fixed order.  The index map and the gather walk are
+//     resize_map.h's, shared with the losses that read the low-resolution map (segloss.hip, regloss.hip).
+#include "resize_map.h"
 
 namespace {
 
@@ -237,25 +238,6 @@ __global__ void __launch_bounds__(256) shuffle_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------------------ resize --
-// PyTorch's upsample_bilinear2d / upsample_nearest2d index math (align_corners = False, no scale_factor): scale = (float)in / out;
-// bilinear: src = max(scale * (dst + 0.5) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1;
-// nearest: i0 = min(floor(dst * scale), in - 1).
-struct Src { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Src src_bilinear(int dst, float scale, int in) {
-    float s = scale * ((float)dst + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    Src r;
-    r.i0 = (int)s;
-    r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-    r.l1 = s - (float)r.i0;
-    r.l0 = 1.0f - r.l1;
-    return r;
-}
-__device__ __forceinline__ int src_nearest(int dst, float scale, int in) {
-    const int i = (int)floorf((float)dst * scale);
-    return i < in - 1 ? i : in - 1;
-}
-
 // out[b][k][oy][ox] from x[b][iy][ix][k] (row stride ldx); each thread 4 consecutive ox of one output row
 template <int BILINEAR>
 __global__ void __launch_bounds__(256) resize_fwd_kernel(const float* __restrict__ x, long long ldx, float* __restrict__ out, int h, int w, int K,
@@ -299,26 +281,8 @@ __global__ void __launch_bounds__(256) resize_fwd_kernel(const float* __restrict
     }
 }
 
-// First output index whose source window reaches input index i (bilinear: i0 >= i - 1 or i1 >= i ... both begin at the first
-// dst with i1(dst) >= i; nearest: i0(dst) >= i).  The estimate from the inverse map is corrected by walking with the exact forward
-// formulas, so the window is the one the forward used.
-template <int BILINEAR>
-__device__ __forceinline__ int first_dst(int i, float scale, int in, int out) {
-    int e = (int)(((float)i - (BILINEAR ? 1.0f : 0.0f)) / scale) - 2;
-    e = e < 0 ? 0 : (e > out - 1 ? out - 1 : e);
-    if (BILINEAR) {
-        while (e > 0 && src_bilinear(e - 1, scale, in).i1 >= i) --e;
-        while (e < out && src_bilinear(e, scale, in).i1 < i) ++e;
-    } else {
-        while (e > 0 && src_nearest(e - 1, scale, in) >= i) --e;
-        while (e < out && src_nearest(e, scale, in) < i) ++e;
-    }
-    return e;
-}
-
 // dx[b][iy][ix][k] (row stride ldx; columns K .. ldx - 1 written as 0) = sum over the output pixels that read (iy, ix) of their
-// weight times g[b][k][oy][ox]: oy ascending, within a row ox ascending, the row sum then weighted -- a fixed order, no atomics.
-// A pixel whose two taps land on the same element (border clamp, i1 == i0) contributes l0 + l1 as the autograd backward does.
+// weight times g[b][k][oy][ox], in resize_gather's fixed order
 template <int BILINEAR>
 __global__ void __launch_bounds__(256) resize_bwd_kernel(const float* __restrict__ g, float* __restrict__ dx, long long ldx, int h, int w, int K,
                                                         int H, int W, float sy, float sx, long long total) {
@@ -332,41 +296,10 @@ __global__ void __launch_bounds__(256) resize_bwd_kernel(const float* __restrict
         float* o = dx + ((b * h + iy) * w + ix) * ldx + k;
         if (k >= K) { *o = 0.f; continue; }
         const float* gb = g + (b * K + k) * (long long)H * W;
-        const int oy0 = first_dst<BILINEAR>(iy, sy, h, H), ox0 = first_dst<BILINEAR>(ix, sx, w, W);
-        float acc = 0.f;
-        for (int oy = oy0; oy < H; ++oy) {
-            float wy;
-            if (BILINEAR) {
-                const Src ry = src_bilinear(oy, sy, h);
-                if (ry.i0 > iy) break;
-                wy = (ry.i0 == iy ? ry.l0 : 0.f) + (ry.i1 == iy ? ry.l1 : 0.f);
-            } else {
-                if (src_nearest(oy, sy, h) > iy) break;
-                wy = 1.f;
-            }
-            const float* gr = gb + (long long)oy * W;
-            float rs = 0.f;
-            for (int ox = ox0; ox < W; ++ox) {
-                if (BILINEAR) {
-                    const Src rx = src_bilinear(ox, sx, w);
-                    if (rx.i0 > ix) break;
-                    const float wx = (rx.i0 == ix ? rx.l0 : 0.f) + (rx.i1 == ix ? rx.l1 : 0.f);
-                    rs = __builtin_fmaf(wx, gr[ox], rs);
-                } else {
-                    if (src_nearest(ox, sx, w) > ix) break;
-                    rs += gr[ox];
-                }
-            }
-            acc = BILINEAR ? __builtin_fmaf(wy, rs, acc) : acc + rs;
-        }
-        *o = acc;
+        *o = resize_gather<BILINEAR>(gb, iy, ix, h, w, H, W, sy, sx, [](float g) { return g; });
     }
 }
 
-inline unsigned grid_for(long long total) {
-    const long long b = (total + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
 inline bool al16(const void* p) { return p == nullptr || ((uintptr_t)p % 16) == 0; }
 
 }  // namespace
@@ -478,30 +411,24 @@ extern "C" int mmae_dwconv7_wgrad(const float* x, const float* dy, float* part, 
 // F.interpolate(x, size=(H, W), mode='bilinear' (mode 0) | 'nearest' (mode 1)) of output_adapters.py:568: x f32 [B][h][w][K] (row stride
 // ldx >= K) -> out f32 NCHW [B][K][H][W]
 extern "C" int mmae_resize_fwd(const float* x, int64_t ldx, float* out, int B, int h, int w, int K, int H, int W, int mode, void* stream) {
-    MMAE_REQUIRE(x && out && B > 0 && h > 0 && w > 0 && K > 0 && H > 0 && W > 0 && ldx >= K && (mode == 0 || mode == 1),
-                 "resize_fwd: bad argument");
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    MMAE_REQUIRE(x && out && resize_geom_ok(B, h, w, K, H, W, ldx, mode), "resize_fwd: bad argument");
+    const ResizeScale sc(h, w, H, W);
     const long long total = (long long)B * K * H * ((W + 3) / 4);
     const int vec = (W % 4 == 0) && al16(out);
-    if (mode == 0)
-        hipLaunchKernelGGL(resize_fwd_kernel<1>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, out, h, w, K, H, W, sy, sx,
-                           total, vec);
-    else
-        hipLaunchKernelGGL(resize_fwd_kernel<0>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, out, h, w, K, H, W, sy, sx,
-                           total, vec);
+    by_mode(mode, [&](auto bl) {
+        hipLaunchKernelGGL(resize_fwd_kernel<decltype(bl)::value>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, out,
+                           h, w, K, H, W, sc.sy, sc.sx, total, vec);
+    });
     return mmae_check_launch("resize_fwd");
 }
 // its backward as a gather: g f32 NCHW [B][K][H][W] -> dx f32 [B][h][w][ldx] (columns K .. ldx - 1 zeroed: a GEMM operand's padding)
 extern "C" int mmae_resize_bwd(const float* g, float* dx, int64_t ldx, int B, int h, int w, int K, int H, int W, int mode, void* stream) {
-    MMAE_REQUIRE(g && dx && B > 0 && h > 0 && w > 0 && K > 0 && H > 0 && W > 0 && ldx >= K && (mode == 0 || mode == 1),
-                 "resize_bwd: bad argument");
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    MMAE_REQUIRE(g && dx && resize_geom_ok(B, h, w, K, H, W, ldx, mode), "resize_bwd: bad argument");
+    const ResizeScale sc(h, w, H, W);
     const long long total = (long long)B * h * w * ldx;
-    if (mode == 0)
-        hipLaunchKernelGGL(resize_bwd_kernel<1>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, g, dx, (long long)ldx, h, w, K, H, W, sy, sx,
-                           total);
-    else
-        hipLaunchKernelGGL(resize_bwd_kernel<0>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, g, dx, (long long)ldx, h, w, K, H, W, sy, sx,
-                           total);
+    by_mode(mode, [&](auto bl) {
+        hipLaunchKernelGGL(resize_bwd_kernel<decltype(bl)::value>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, g, dx, (long long)ldx,
+                           h, w, K, H, W, sc.sy, sc.sx, total);
+    });
     return mmae_check_launch("resize_bwd");
 }

@@ -6,48 +6,18 @@
 //                   berHu takes a second pass over the stored difference once c = max(0.2 max|d|, 1e-5) is known
 //   reg_loss_bwd    the gradient with respect to the low-resolution map: the gather form of resize_bwd_kernel over g(d)
 //   depth_metrics   the eight sums behind rmse, rel, srel, log10, delta_1..3 in one pass, the ratios in a finish kernel
-// The interpolation uses the index math of csrc/convnext.hip (src_bilinear / src_nearest / first_dst) and combines the four taps with
-// the function resize_fwd_kernel calls (common.h resize_tap4: every rounding written out), so the value the loss sees is the pixel
-// mmae_resize_fwd would store (tests/test_reg_loss_gpu.py checks the bits).
+// The interpolation takes its taps and weights from resize_map.h -- the functions resize_fwd_kernel calls -- and combines the four
+// taps with common.h's resize_tap4 as that kernel does (every rounding written out), so the value the loss sees is the pixel
+// mmae_resize_fwd would store (tests/test_reg_loss_gpu.py checks the bits); the backward is resize_map.h's gather walk over g(d).
 //
 // Work shape: K is 1 (depth) or 3 (normals, rgb), so pixels, not channels, lie on the lanes: one thread per output pixel, lanes along
 // ox (coalesced target / mask / difference accesses; the low-resolution rows come from cache), a short loop over k <= MMAE_REG_MAX_K.
 // In-wave reductions by wave64 shuffles, LDS only to join the four waves in wave order, no float atomics: run-to-run results are
 // bit-equal.  Columns K .. ldx - 1 of the map are never read.
-#include "common.h"
-#include <math.h>
+#include "resize_map.h"
 
 namespace {
 
-// ---- index math of csrc/convnext.hip (its source coordinate's product and sum contract to one FMA: spelled out here) ------------
-struct Src { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Src src_bilinear(int dst, float scale, int in) {
-    float s = __builtin_fmaf(scale, (float)dst + 0.5f, -0.5f);
-    s = s < 0.f ? 0.f : s;
-    Src r;
-    r.i0 = (int)s;
-    r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-    r.l1 = s - (float)r.i0;
-    r.l0 = 1.0f - r.l1;
-    return r;
-}
-__device__ __forceinline__ int src_nearest(int dst, float scale, int in) {
-    const int i = (int)floorf((float)dst * scale);
-    return i < in - 1 ? i : in - 1;
-}
-template <int BILINEAR>
-__device__ __forceinline__ int first_dst(int i, float scale, int in, int out) {
-    int e = (int)(((float)i - (BILINEAR ? 1.0f : 0.0f)) / scale) - 2;
-    e = e < 0 ? 0 : (e > out - 1 ? out - 1 : e);
-    if (BILINEAR) {
-        while (e > 0 && src_bilinear(e - 1, scale, in).i1 >= i) --e;
-        while (e < out && src_bilinear(e, scale, in).i1 < i) ++e;
-    } else {
-        while (e > 0 && src_nearest(e - 1, scale, in) >= i) --e;
-        while (e < out && src_nearest(e, scale, in) < i) ++e;
-    }
-    return e;
-}
 constexpr int WAVES = 4;                      // waves per workgroup (256 threads)
 enum { KIND_L1 = 0, KIND_MSE = 1, KIND_BERHU = 2 };
 
@@ -77,9 +47,6 @@ struct Taps {
         return x[o00 + k];
     }
 };
-
-// the four waves' values joined in wave order by thread 0 (sh: WAVES floats per quantity)
-__device__ __forceinline__ float join_sum(const float* sh) { return ((sh[0] + sh[1]) + sh[2]) + sh[3]; }
 
 // diff[b][k][oy][ox] = mask ? z - target : 0;  partial[4 i .. 4 i + 3] = workgroup i's sum |d|, sum d^2, max |d|, valid count
 template <int BILINEAR>
@@ -119,19 +86,10 @@ __global__ void __launch_bounds__(256) reg_fwd_kernel(const float* __restrict__ 
     __syncthreads();
     if (threadIdx.x == 0) {
         float* p = partial + 4 * (long long)blockIdx.x;
-        p[0] = join_sum(sh);
-        p[1] = join_sum(sh + WAVES);
-        p[2] = fmaxf(fmaxf(sh[2 * WAVES], sh[2 * WAVES + 1]), fmaxf(sh[2 * WAVES + 2], sh[2 * WAVES + 3]));
-        p[3] = join_sum(sh + 3 * WAVES);
-    }
-}
-
-// a fixed tree over 256 doubles held in LDS; the result in s[0]
-__device__ __forceinline__ void tree_sum(double* s) {
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-        __syncthreads();
+        p[0] = join4_sum(sh);
+        p[1] = join4_sum(sh + WAVES);
+        p[2] = join4_max(sh + 2 * WAVES);
+        p[3] = join4_sum(sh + 3 * WAVES);
     }
 }
 
@@ -149,23 +107,16 @@ __global__ void __launch_bounds__(256) reg_finish_kernel(const float* __restrict
         mm = fmaxf(mm, partial[4 * i + 2]);
         n += (double)partial[4 * i + 3];
     }
-    s[threadIdx.x] = a;
-    q[threadIdx.x] = b;
-    c[threadIdx.x] = n;
-    m[threadIdx.x] = mm;
-    tree_sum(s);
-    tree_sum(q);
-    tree_sum(c);
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) m[threadIdx.x] = fmaxf(m[threadIdx.x], m[threadIdx.x + o]);
-        __syncthreads();
-    }
+    a = block_tree_sum(a, s);
+    b = block_tree_sum(b, q);
+    n = block_tree_sum(n, c);
+    mm = block_tree_max(mm, m);
     if (threadIdx.x == 0) {
-        const double sum = kind == KIND_MSE ? q[0] : s[0];
-        out[0] = c[0] > 0.0 ? (float)(sum / c[0]) : 0.f;
-        out[1] = (float)c[0];
-        out[2] = m[0];
-        out[3] = fmaxf(0.2f * m[0], 1e-5f);
+        const double sum = kind == KIND_MSE ? b : a;
+        out[0] = n > 0.0 ? (float)(sum / n) : 0.f;
+        out[1] = (float)n;
+        out[2] = mm;
+        out[3] = fmaxf(0.2f * mm, 1e-5f);
     }
 }
 
@@ -184,16 +135,15 @@ __global__ void __launch_bounds__(256) reg_berhu_kernel(const float* __restrict_
     s = wave_sum(s);
     if (lane == 0) sh[wave] = s;
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = join_sum(sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = join4_sum(sh);
 }
 
 __global__ void __launch_bounds__(256) reg_berhu_finish_kernel(const float* __restrict__ partial, int nb, float* __restrict__ out) {
     __shared__ double s[256];
     double a = 0.0;
     for (int i = threadIdx.x; i < nb; i += 256) a += (double)partial[i];
-    s[threadIdx.x] = a;
-    tree_sum(s);
-    if (threadIdx.x == 0) out[0] = out[1] > 0.f ? (float)(s[0] / (double)out[1]) : 0.f;
+    a = block_tree_sum(a, s);
+    if (threadIdx.x == 0) out[0] = out[1] > 0.f ? (float)(a / (double)out[1]) : 0.f;
 }
 
 // d(loss sum) / d(difference): L1 sign(d) with sign(0) = 0 (torch's abs gradient), MSE 2 d, berHu sign(d) inside |d| < c and d / c
@@ -223,33 +173,7 @@ __global__ void __launch_bounds__(256) reg_bwd_kernel(const float* __restrict__ 
         const int iy = (int)(q % h);
         const long long b = q / h;
         const float* gb = diff + (b * K + k) * (long long)H * W;
-        const int oy0 = first_dst<BILINEAR>(iy, sy, h, H), ox0 = first_dst<BILINEAR>(ix, sx, w, W);
-        float acc = 0.f;
-        for (int oy = oy0; oy < H; ++oy) {
-            float wy;
-            if (BILINEAR) {
-                const Src ry = src_bilinear(oy, sy, h);
-                if (ry.i0 > iy) break;
-                wy = (ry.i0 == iy ? ry.l0 : 0.f) + (ry.i1 == iy ? ry.l1 : 0.f);
-            } else {
-                if (src_nearest(oy, sy, h) > iy) break;
-                wy = 1.f;
-            }
-            const float* gr = gb + (long long)oy * W;
-            float rs = 0.f;
-            for (int ox = ox0; ox < W; ++ox) {
-                if (BILINEAR) {
-                    const Src rx = src_bilinear(ox, sx, w);
-                    if (rx.i0 > ix) break;
-                    const float wx = (rx.i0 == ix ? rx.l0 : 0.f) + (rx.i1 == ix ? rx.l1 : 0.f);
-                    rs = __builtin_fmaf(wx, g_of<KIND>(gr[ox], c), rs);
-                } else {
-                    if (src_nearest(ox, sx, w) > ix) break;
-                    rs += g_of<KIND>(gr[ox], c);
-                }
-            }
-            acc = BILINEAR ? __builtin_fmaf(wy, rs, acc) : acc + rs;
-        }
+        const float acc = resize_gather<BILINEAR>(gb, iy, ix, h, w, H, W, sy, sx, [c](float d) { return g_of<KIND>(d, c); });
         float* o = dx + p * ldx;
         o[k] = acc * scale;
         if (k == K - 1)
@@ -300,7 +224,7 @@ __global__ void __launch_bounds__(256) depth_metrics_kernel(const float* __restr
         if (lane == 0) sh[j * WAVES + wave] = v;
     }
     __syncthreads();
-    if (threadIdx.x < 8) partial[8 * (long long)blockIdx.x + threadIdx.x] = join_sum(sh + threadIdx.x * WAVES);
+    if (threadIdx.x < 8) partial[8 * (long long)blockIdx.x + threadIdx.x] = join4_sum(sh + threadIdx.x * WAVES);
 }
 
 // out[7] = rmse, rel, srel, log10 (the natural log, as the reference's key), delta_1, delta_2, delta_3 from the partials summed in
@@ -311,17 +235,16 @@ __global__ void __launch_bounds__(256) depth_metrics_finish_kernel(const float* 
     double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = threadIdx.x; i < nb; i += 256)
         for (int j = 0; j < 8; ++j) a[j] += (double)partial[8 * i + j];
-    for (int j = 0; j < 8; ++j) s[j][threadIdx.x] = a[j];
-    for (int j = 0; j < 8; ++j) tree_sum(s[j]);
+    for (int j = 0; j < 8; ++j) a[j] = block_tree_sum(a[j], s[j]);
     if (threadIdx.x == 0) {
-        const double n = s[0][0];
-        out[0] = (float)sqrt(s[1][0] / n);
-        out[1] = (float)(s[2][0] / n);
-        out[2] = (float)(s[3][0] / n);
-        out[3] = (float)sqrt(s[4][0] / n);
-        out[4] = (float)(s[5][0] / n);
-        out[5] = (float)(s[6][0] / n);
-        out[6] = (float)(s[7][0] / n);
+        const double n = a[0];
+        out[0] = (float)sqrt(a[1] / n);
+        out[1] = (float)(a[2] / n);
+        out[2] = (float)(a[3] / n);
+        out[3] = (float)sqrt(a[4] / n);
+        out[4] = (float)(a[5] / n);
+        out[5] = (float)(a[6] / n);
+        out[6] = (float)(a[7] / n);
         if (acc != nullptr) {
             for (int j = 0; j < 7; ++j) acc[j] += out[j];
             acc[7] += 1.f;
@@ -329,47 +252,34 @@ __global__ void __launch_bounds__(256) depth_metrics_finish_kernel(const float* 
     }
 }
 
-inline unsigned grid_for(long long total) {
-    const long long b = (total + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > MMAE_REG_PARTIALS ? MMAE_REG_PARTIALS : b));
-}
-inline bool geom_ok(int B, int h, int w, int K, int H, int W, int64_t ldx, int mode) {
-    return B > 0 && h > 0 && w > 0 && K > 0 && K <= MMAE_REG_MAX_K && H > 0 && W > 0 && ldx >= K && (mode == 0 || mode == 1);
-}
-
-template <int BILINEAR>
-void launch_bwd(int kind, unsigned nb, hipStream_t st, const float* diff, const float* out, const float* up, float* dx, long long ldx, int h,
-                int w, int K, int H, int W, float sy, float sx, long long total) {
-    if (kind == KIND_L1)
-        hipLaunchKernelGGL((reg_bwd_kernel<BILINEAR, KIND_L1>), dim3(nb), dim3(256), 0, st, diff, out, up, dx, ldx, h, w, K, H, W, sy, sx, total);
-    else if (kind == KIND_MSE)
-        hipLaunchKernelGGL((reg_bwd_kernel<BILINEAR, KIND_MSE>), dim3(nb), dim3(256), 0, st, diff, out, up, dx, ldx, h, w, K, H, W, sy, sx, total);
-    else
-        hipLaunchKernelGGL((reg_bwd_kernel<BILINEAR, KIND_BERHU>), dim3(nb), dim3(256), 0, st, diff, out, up, dx, ldx, h, w, K, H, W, sy, sx,
-                           total);
+// launch(std::integral_constant<int, KIND>) for the kind
+template <class F>
+void by_kind(int kind, F&& launch) {
+    if (kind == KIND_L1) launch(std::integral_constant<int, KIND_L1>{});
+    else if (kind == KIND_MSE) launch(std::integral_constant<int, KIND_MSE>{});
+    else launch(std::integral_constant<int, KIND_BERHU>{});
 }
 
 }  // namespace
 
 extern "C" int mmae_reg_loss_fwd(const float* x, int64_t ldx, const float* target, const void* mask, int mask_channels, int kind, int B, int h,
                                  int w, int K, int H, int W, int mode, float* diff, float* partial, float* out, void* stream) {
-    MMAE_REQUIRE(x && target && diff && partial && out && geom_ok(B, h, w, K, H, W, ldx, mode), "reg_loss_fwd: bad argument (K <= 16)");
+    MMAE_REQUIRE(x && target && diff && partial && out && resize_geom_ok(B, h, w, K, H, W, ldx, mode) && K <= MMAE_REG_MAX_K,
+                 "reg_loss_fwd: bad argument (K <= 16)");
     MMAE_REQUIRE(kind >= KIND_L1 && kind <= KIND_BERHU, "reg_loss_fwd: kind is 0 (L1), 1 (MSE) or 2 (berHu)");
     MMAE_REQUIRE(mask == nullptr || mask_channels == 1 || mask_channels == K, "reg_loss_fwd: the mask has 1 or K channels");
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    const ResizeScale sc(h, w, H, W);
     const long long total = (long long)B * H * W;
-    const unsigned nb = grid_for(total);
+    const unsigned nb = grid_for(total, MMAE_REG_PARTIALS);
     hipStream_t st = (hipStream_t)stream;
-    if (mode == 0)
-        hipLaunchKernelGGL(reg_fwd_kernel<1>, dim3(nb), dim3(256), 0, st, x, (long long)ldx, target, (const unsigned char*)mask, mask_channels,
-                           diff, partial, h, w, K, H, W, sy, sx, total);
-    else
-        hipLaunchKernelGGL(reg_fwd_kernel<0>, dim3(nb), dim3(256), 0, st, x, (long long)ldx, target, (const unsigned char*)mask, mask_channels,
-                           diff, partial, h, w, K, H, W, sy, sx, total);
+    by_mode(mode, [&](auto bl) {
+        hipLaunchKernelGGL(reg_fwd_kernel<decltype(bl)::value>, dim3(nb), dim3(256), 0, st, x, (long long)ldx, target, (const unsigned char*)mask,
+                           mask_channels, diff, partial, h, w, K, H, W, sc.sy, sc.sx, total);
+    });
     hipLaunchKernelGGL(reg_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)partial, (int)nb, kind, out);
     if (kind == KIND_BERHU) {
         const long long n = total * K;
-        const unsigned nb2 = grid_for(n);
+        const unsigned nb2 = grid_for(n, MMAE_REG_PARTIALS);
         hipLaunchKernelGGL(reg_berhu_kernel, dim3(nb2), dim3(256), 0, st, (const float*)diff, (const float*)out, partial, n);
         hipLaunchKernelGGL(reg_berhu_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)partial, (int)nb2, out);
     }
@@ -378,32 +288,31 @@ extern "C" int mmae_reg_loss_fwd(const float* x, int64_t ldx, const float* targe
 
 extern "C" int mmae_reg_loss_bwd(const float* diff, const float* out, const float* up, int kind, int B, int h, int w, int K, int H, int W,
                                  int mode, float* dx, int64_t ldx, void* stream) {
-    MMAE_REQUIRE(diff && out && up && dx && geom_ok(B, h, w, K, H, W, ldx, mode), "reg_loss_bwd: bad argument (K <= 16)");
+    MMAE_REQUIRE(diff && out && up && dx && resize_geom_ok(B, h, w, K, H, W, ldx, mode) && K <= MMAE_REG_MAX_K,
+                 "reg_loss_bwd: bad argument (K <= 16)");
     MMAE_REQUIRE(kind >= KIND_L1 && kind <= KIND_BERHU, "reg_loss_bwd: kind is 0 (L1), 1 (MSE) or 2 (berHu)");
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    const ResizeScale sc(h, w, H, W);
     const long long total = (long long)B * h * w * K;
-    const long long blocks = (total + 255) / 256;
-    const unsigned nb = (unsigned)(blocks > 65536 ? 65536 : blocks);
-    if (mode == 0)
-        launch_bwd<1>(kind, nb, (hipStream_t)stream, diff, out, up, dx, (long long)ldx, h, w, K, H, W, sy, sx, total);
-    else
-        launch_bwd<0>(kind, nb, (hipStream_t)stream, diff, out, up, dx, (long long)ldx, h, w, K, H, W, sy, sx, total);
+    by_mode(mode, [&](auto bl) {
+        by_kind(kind, [&](auto kd) {
+            hipLaunchKernelGGL((reg_bwd_kernel<decltype(bl)::value, decltype(kd)::value>), dim3(grid_for(total)), dim3(256), 0,
+                               (hipStream_t)stream, diff, out, up, dx, (long long)ldx, h, w, K, H, W, sc.sy, sc.sx, total);
+        });
+    });
     return mmae_check_launch("reg_loss_bwd");
 }
 
 extern "C" int mmae_depth_metrics(const float* x, int64_t ldx, const float* target, const void* mask, float mean, float std, int B, int h, int w,
                                   int H, int W, int mode, float* partial, float* out, float* acc, void* stream) {
-    MMAE_REQUIRE(x && target && partial && out && geom_ok(B, h, w, 1, H, W, ldx, mode), "depth_metrics: bad argument");
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    MMAE_REQUIRE(x && target && partial && out && resize_geom_ok(B, h, w, 1, H, W, ldx, mode), "depth_metrics: bad argument");
+    const ResizeScale sc(h, w, H, W);
     const long long total = (long long)B * H * W;
-    const unsigned nb = grid_for(total);
+    const unsigned nb = grid_for(total, MMAE_REG_PARTIALS);
     hipStream_t st = (hipStream_t)stream;
-    if (mode == 0)
-        hipLaunchKernelGGL(depth_metrics_kernel<1>, dim3(nb), dim3(256), 0, st, x, (long long)ldx, target, (const unsigned char*)mask, mean, std,
-                           partial, h, w, H, W, sy, sx, total);
-    else
-        hipLaunchKernelGGL(depth_metrics_kernel<0>, dim3(nb), dim3(256), 0, st, x, (long long)ldx, target, (const unsigned char*)mask, mean, std,
-                           partial, h, w, H, W, sy, sx, total);
+    by_mode(mode, [&](auto bl) {
+        hipLaunchKernelGGL(depth_metrics_kernel<decltype(bl)::value>, dim3(nb), dim3(256), 0, st, x, (long long)ldx, target,
+                           (const unsigned char*)mask, mean, std, partial, h, w, H, W, sc.sy, sc.sx, total);
+    });
     hipLaunchKernelGGL(depth_metrics_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)partial, (int)nb, out, acc);
     return mmae_check_launch("depth_metrics");
 }

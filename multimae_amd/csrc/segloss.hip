@@ -6,48 +6,21 @@
 //   seg_hist     the four histograms of the reference's intersect_and_union (utils/semseg_metrics.py:49-59), added into an int64 buffer.
 //                np.histogram's closed last bin would count a value exactly equal to K into class K - 1; that quirk is NOT reproduced:
 //                a prediction or label outside [0, K) is dropped.
-// The interpolation is written with the expressions of csrc/convnext.hip (src_bilinear / src_nearest / first_dst and the four-tap form
-// of resize_fwd_kernel), so the value the loss sees is the pixel mmae_resize_fwd would store (tests/test_seg_loss_gpu.py checks the
-// bits).  A target outside [0, K) that is not ignore_index counts as ignored (csrc/losses.hip; torch raises a device assert).
+// The interpolation takes its taps and weights from resize_map.h, the functions resize_fwd_kernel calls.  It combines the four taps
+// with its own tap4 below, which is left to the compiler's contraction, NOT with common.h's resize_tap4 as that kernel does: an
+// interpolated logit lies within test_resize_fwd's bound of the pixel mmae_resize_fwd would store, not on its bits.  What is
+// guaranteed and tested (tests/test_seg_loss_gpu.py) is that seg_argmax agrees with the argmax of the written image.  Calling
+// resize_tap4 here would move lse, loss and gradient by ulps: a change of behaviour, not done in passing.
+// A target outside [0, K) that is not ignore_index counts as ignored (csrc/losses.hip; torch raises a device assert).
 //
 // Work shape: one wave per output pixel (forward, argmax) or per low-resolution pixel and 64-class chunk (backward), lanes over classes,
 // so every logit row is read as coalesced 256-byte segments and a lane owns its accumulator.  No float atomics, no LDS accumulators:
 // run-to-run results are bit-equal.  The low-resolution logits (39 MB at the ADE20K geometry) stay in the L2 / Infinity Cache.
-#include "common.h"
-#include <math.h>
+#include "resize_map.h"
 
 namespace {
 
-// ---- index math of csrc/convnext.hip, verbatim ---------------------------------------------------------------------------------
-struct Src { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Src src_bilinear(int dst, float scale, int in) {
-    float s = scale * ((float)dst + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    Src r;
-    r.i0 = (int)s;
-    r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-    r.l1 = s - (float)r.i0;
-    r.l0 = 1.0f - r.l1;
-    return r;
-}
-__device__ __forceinline__ int src_nearest(int dst, float scale, int in) {
-    const int i = (int)floorf((float)dst * scale);
-    return i < in - 1 ? i : in - 1;
-}
-template <int BILINEAR>
-__device__ __forceinline__ int first_dst(int i, float scale, int in, int out) {
-    int e = (int)(((float)i - (BILINEAR ? 1.0f : 0.0f)) / scale) - 2;
-    e = e < 0 ? 0 : (e > out - 1 ? out - 1 : e);
-    if (BILINEAR) {
-        while (e > 0 && src_bilinear(e - 1, scale, in).i1 >= i) --e;
-        while (e < out && src_bilinear(e, scale, in).i1 < i) ++e;
-    } else {
-        while (e > 0 && src_nearest(e - 1, scale, in) >= i) --e;
-        while (e < out && src_nearest(e, scale, in) < i) ++e;
-    }
-    return e;
-}
-// the four taps as resize_fwd_kernel combines them (a, b: row i0 at columns i0, i1; c, d: row i1)
+// the four taps (a, b: row i0 at columns i0, i1; c, d: row i1) in resize_fwd_kernel's form, its roundings left to the compiler
 __device__ __forceinline__ float tap4(const Src& ry, const Src& rx, float a, float b, float c, float d) {
     return ry.l0 * (rx.l0 * a + rx.l1 * b) + ry.l1 * (rx.l0 * c + rx.l1 * d);
 }
@@ -136,8 +109,8 @@ __global__ void __launch_bounds__(256) seg_ce_fwd_kernel(const float* __restrict
     if (lane == 0) { sh[wave] = sum; sh[WAVES + wave] = cnt; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-        partial[2 * blockIdx.x + 1] = ((sh[4] + sh[5]) + sh[6]) + sh[7];
+        partial[2 * blockIdx.x] = join4_sum(sh);
+        partial[2 * blockIdx.x + 1] = join4_sum(sh + WAVES);
     }
 }
 
@@ -146,16 +119,11 @@ __global__ void __launch_bounds__(256) seg_ce_finish_kernel(const float* __restr
     __shared__ double s[256], c[256];
     double a = 0.0, n = 0.0;
     for (int i = threadIdx.x; i < nb; i += 256) { a += (double)partial[2 * i]; n += (double)partial[2 * i + 1]; }
-    s[threadIdx.x] = a;
-    c[threadIdx.x] = n;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { s[threadIdx.x] += s[threadIdx.x + o]; c[threadIdx.x] += c[threadIdx.x + o]; }
-        __syncthreads();
-    }
+    a = block_tree_sum(a, s);
+    n = block_tree_sum(n, c);
     if (threadIdx.x == 0) {
-        out[0] = c[0] > 0.0 ? (float)(s[0] / c[0]) : 0.f;
-        out[1] = (float)c[0];
+        out[0] = n > 0.0 ? (float)(a / n) : 0.f;
+        out[1] = (float)n;
     }
 }
 
@@ -320,62 +288,45 @@ __global__ void __launch_bounds__(256) seg_hist_kernel(const long long* __restri
     }
 }
 
-inline unsigned wave_grid(long long tasks) {
-    const long long b = (tasks + WAVES - 1) / WAVES;
-    return (unsigned)(b < 1 ? 1 : (b > MMAE_SEG_PARTIALS ? MMAE_SEG_PARTIALS : b));
-}
-inline bool geom_ok(int B, int h, int w, int K, int H, int W, int64_t ldx, int mode) {
-    return B > 0 && h > 0 && w > 0 && K > 0 && H > 0 && W > 0 && ldx >= K && (mode == 0 || mode == 1);
-}
-
 }  // namespace
 
 extern "C" int mmae_seg_ce_fwd(const float* x, int64_t ldx, const int64_t* target, int64_t ignore_index, int B, int h, int w, int K, int H, int W,
                                int mode, float* lse, float* partial, float* out, void* stream) {
-    MMAE_REQUIRE(x && target && lse && partial && out && geom_ok(B, h, w, K, H, W, ldx, mode), "seg_ce_fwd: bad argument");
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    MMAE_REQUIRE(x && target && lse && partial && out && resize_geom_ok(B, h, w, K, H, W, ldx, mode), "seg_ce_fwd: bad argument");
+    const ResizeScale sc(h, w, H, W);
     const long long tasks = (long long)B * H * ((W + RUN - 1) / RUN);
-    const unsigned nb = wave_grid(tasks);
-    if (mode == 0)
-        hipLaunchKernelGGL(seg_ce_fwd_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, (const long long*)target,
-                           (long long)ignore_index, lse, partial, h, w, K, H, W, sy, sx, tasks);
-    else
-        hipLaunchKernelGGL(seg_ce_fwd_kernel<0>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, (const long long*)target,
-                           (long long)ignore_index, lse, partial, h, w, K, H, W, sy, sx, tasks);
+    const unsigned nb = grid_for(tasks, MMAE_SEG_PARTIALS, WAVES);
+    by_mode(mode, [&](auto bl) {
+        hipLaunchKernelGGL(seg_ce_fwd_kernel<decltype(bl)::value>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx,
+                           (const long long*)target, (long long)ignore_index, lse, partial, h, w, K, H, W, sc.sy, sc.sx, tasks);
+    });
     hipLaunchKernelGGL(seg_ce_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, (int)nb, out);
     return mmae_check_launch("seg_ce_fwd");
 }
 
 extern "C" int mmae_seg_ce_bwd(const float* x, int64_t ldx, const int64_t* target, int64_t ignore_index, int B, int h, int w, int K, int H, int W,
                                int mode, const float* lse, const float* out, const float* up, float* dx, void* stream) {
-    MMAE_REQUIRE(x && target && lse && out && up && dx && geom_ok(B, h, w, K, H, W, ldx, mode), "seg_ce_bwd: bad argument");
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    MMAE_REQUIRE(x && target && lse && out && up && dx && resize_geom_ok(B, h, w, K, H, W, ldx, mode), "seg_ce_bwd: bad argument");
+    const ResizeScale sc(h, w, H, W);
     const int nch = (int)((ldx + 63) / 64);
     const long long tasks = (long long)B * h * w * nch;
-    const long long blocks = (tasks + WAVES - 1) / WAVES;
-    const unsigned nb = (unsigned)(blocks > 65536 ? 65536 : blocks);
-    if (mode == 0)
-        hipLaunchKernelGGL(seg_ce_bwd_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, (const long long*)target,
-                           (long long)ignore_index, lse, out, up, dx, h, w, K, H, W, sy, sx, nch, tasks);
-    else
-        hipLaunchKernelGGL(seg_ce_bwd_kernel<0>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, (const long long*)target,
-                           (long long)ignore_index, lse, out, up, dx, h, w, K, H, W, sy, sx, nch, tasks);
+    by_mode(mode, [&](auto bl) {
+        hipLaunchKernelGGL(seg_ce_bwd_kernel<decltype(bl)::value>, dim3(grid_for(tasks, 65536, WAVES)), dim3(256), 0, (hipStream_t)stream, x,
+                           (long long)ldx, (const long long*)target, (long long)ignore_index, lse, out, up, dx, h, w, K, H, W, sc.sy, sc.sx, nch,
+                           tasks);
+    });
     return mmae_check_launch("seg_ce_bwd");
 }
 
 extern "C" int mmae_seg_argmax(const float* x, int64_t ldx, int B, int h, int w, int K, int n_cls, int H, int W, int mode, int64_t* pred,
                                void* stream) {
-    MMAE_REQUIRE(x && pred && geom_ok(B, h, w, K, H, W, ldx, mode) && n_cls > 0 && n_cls <= K, "seg_argmax: bad argument");
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    MMAE_REQUIRE(x && pred && resize_geom_ok(B, h, w, K, H, W, ldx, mode) && n_cls > 0 && n_cls <= K, "seg_argmax: bad argument");
+    const ResizeScale sc(h, w, H, W);
     const long long tasks = (long long)B * H * ((W + RUN - 1) / RUN);
-    const long long blocks = (tasks + WAVES - 1) / WAVES;
-    const unsigned nb = (unsigned)(blocks > 65536 ? 65536 : blocks);
-    if (mode == 0)
-        hipLaunchKernelGGL(seg_argmax_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, (long long*)pred, h, w, n_cls, H, W,
-                           sy, sx, tasks);
-    else
-        hipLaunchKernelGGL(seg_argmax_kernel<0>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, (long long*)pred, h, w, n_cls, H, W,
-                           sy, sx, tasks);
+    by_mode(mode, [&](auto bl) {
+        hipLaunchKernelGGL(seg_argmax_kernel<decltype(bl)::value>, dim3(grid_for(tasks, 65536, WAVES)), dim3(256), 0, (hipStream_t)stream, x,
+                           (long long)ldx, (long long*)pred, h, w, n_cls, H, W, sc.sy, sc.sx, tasks);
+    });
     return mmae_check_launch("seg_argmax");
 }
 

@@ -1373,6 +1373,26 @@ class ConvNeXtHeadFn(torch.autograd.Function):
         return (None, d_enc, *grads)
 
 
+def _lowres_loss_forward(ctx, h: SegHandle, target: Tensor, fwd):
+    """what SegCEFn and RegLossFn share going forward: fwd(target) -> (the backward's workspace, out); the loss is out[0]"""
+    ops._require_gpu(h.logits, 'loss input')
+    ws, out = fwd(target)
+    ctx.saved = (h, target, ws, out, target._version)
+    return out[0].clone()
+
+
+def _lowres_loss_backward(ctx, g: Tensor, what: str, bwd, n_rest: int):
+    """... and going back: bwd(h, target, ws, out, up) -> the gradient of the low-resolution map, handed to the head as h.d_logits"""
+    h, target, ws, out, version = ctx.saved
+    ctx.saved = None
+    if target._version != version:
+        raise RuntimeError(f'a tensor saved for the {what}-loss backward was modified in place')
+    up = g.contiguous().float().reshape(1)
+    d = bwd(h, target, ws, out, up)
+    h.d_logits = d if h.d_logits is None else h.d_logits.add_(d)         # several losses on one prediction: their gradients add
+    return (up.new_empty(1),) + (None,) * n_rest
+
+
 class SegCEFn(torch.autograd.Function):
     """nn.CrossEntropyLoss(ignore_index, reduction='mean') on the ConvNeXt head's low-resolution logits (SegHandle): the interpolation
     happens inside the loss kernels (csrc/segloss.hip), the gradient goes back to the head as d_logits.  A target outside [0, K) counts
@@ -1380,23 +1400,13 @@ class SegCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, token: Tensor, h: SegHandle, target: Tensor, ignore_index: int):
-        ops._require_gpu(h.logits, 'loss input')
-        target = target.contiguous().long()
-        lse, out = ops.seg_ce_fwd(h.logits, h.ld, target, ignore_index, *h.geom())
-        ctx.saved = (h, target, lse, out, target._version)
         ctx.ignore_index = int(ignore_index)
-        return out[0].clone()
+        return _lowres_loss_forward(ctx, h, target.contiguous().long(), lambda t: ops.seg_ce_fwd(h.logits, h.ld, t, ignore_index, *h.geom()))
 
     @staticmethod
     def backward(ctx, g: Tensor):
-        h, target, lse, out, version = ctx.saved
-        ctx.saved = None
-        if target._version != version:
-            raise RuntimeError('a tensor saved for the segmentation-loss backward was modified in place')
-        up = g.contiguous().float().reshape(1)
-        d = ops.seg_ce_bwd(h.logits, h.ld, target, ctx.ignore_index, *h.geom(), lse, out, up, torch.empty_like(h.logits))
-        h.d_logits = d if h.d_logits is None else h.d_logits.add_(d)     # several losses on one prediction: their gradients add
-        return up.new_empty(1), None, None, None
+        return _lowres_loss_backward(ctx, g, 'segmentation', lambda h, target, lse, out, up: ops.seg_ce_bwd(
+            h.logits, h.ld, target, ctx.ignore_index, *h.geom(), lse, out, up, torch.empty_like(h.logits)), 3)
 
 
 class RegLossFn(torch.autograd.Function):
@@ -1407,25 +1417,14 @@ class RegLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, token: Tensor, h: SegHandle, target: Tensor, mask: Optional[Tensor], kind: str):
-        ops._require_gpu(h.logits, 'loss input')
-        target = target.contiguous()
-        if mask is not None:
-            mask = mask.contiguous()
-        diff, out = ops.reg_loss_fwd(h.logits, h.ld, target, mask, kind, *h.geom())
-        ctx.saved = (h, target, diff, out, target._version)
         ctx.kind = kind
-        return out[0].clone()
+        mask = None if mask is None else mask.contiguous()
+        return _lowres_loss_forward(ctx, h, target.contiguous(), lambda t: ops.reg_loss_fwd(h.logits, h.ld, t, mask, kind, *h.geom()))
 
     @staticmethod
     def backward(ctx, g: Tensor):
-        h, target, diff, out, version = ctx.saved
-        ctx.saved = None
-        if target._version != version:
-            raise RuntimeError('a tensor saved for the regression-loss backward was modified in place')
-        up = g.contiguous().float().reshape(1)
-        d = ops.reg_loss_bwd(diff, out, up, ctx.kind, *h.geom(), torch.empty_like(h.logits), h.ld)
-        h.d_logits = d if h.d_logits is None else h.d_logits.add_(d)     # several losses on one prediction: their gradients add
-        return up.new_empty(1), None, None, None, None
+        return _lowres_loss_backward(ctx, g, 'regression', lambda h, target, diff, out, up: ops.reg_loss_bwd(
+            diff, out, up, ctx.kind, *h.geom(), torch.empty_like(h.logits), h.ld), 4)
 
 
 class SoftCEFn(torch.autograd.Function):
