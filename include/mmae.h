@@ -678,13 +678,13 @@ int mmae_patch_rows(const mmae_patch_src* srcs_host, const int32_t* task_offsets
                     void* rows, int rows_dtype, int B, int n_sel, int Ktot, void* stream);
 /* d_emb[cls][e] += d_rows[row][k_off + e*ph*pw + i*pw + j] over the selected tokens in
  * [tok_off, tok_off + n_patches); d_rows [B*n_sel][ld], rows_dtype MMAE_BF16 / MMAE_F32 (any other code, MMAE_F16 included, is
- * refused with MMAE_ESUPPORT before anything is written).  (float atomics) */
+ * refused with MMAE_ESUPPORT before anything is written, and so is a table n_cls * E * 4 bytes beyond the 160 KiB LDS).  (float atomics) */
 int mmae_semseg_emb_bwd(const void* d_rows, int rows_dtype, int64_t ld, const int64_t* cls, const int64_t* sel, float* d_emb,
                         int B, int H, int W, int E, int ph, int pw, int n_sel, int k_off, int tok_off, int n_patches, int n_cls,
                         void* stream);
 /* The same gradient without atomics: every table entry is summed in a fixed order (per-thread columns of workgroup-private LDS tables, partial
  * tables per workgroup in ws, a second launch that sums them in index order) -- bit-identical from run to run.  ws: f32 scratch of
- * mmae_semseg_emb_bwd_ws_elems() elements (-1: geometry not supported); accumulate 0: d_emb = gradient (no zero-fill needed), 1: d_emb += gradient.
+ * mmae_semseg_emb_bwd_ws_elems() elements (-1: geometry not supported, B * n_sel = 0 rows included); accumulate 0: d_emb = gradient (no zero-fill needed), 1: d_emb += gradient.
  * rows_dtype MMAE_BF16 / MMAE_F32.  ABI v7. */
 int64_t mmae_semseg_emb_bwd_ws_elems(int B, int n_sel, int E, int n_cls);
 int mmae_semseg_emb_bwd_det(const void* d_rows, int rows_dtype, int64_t ld, const int64_t* cls, const int64_t* sel, float* d_emb,

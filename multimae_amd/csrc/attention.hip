@@ -25,7 +25,7 @@
 //
 // Replaces Attention.forward / CrossAttention.forward cores (multimae_utils.py:175-179, 206-210) + autograd.
 #include "common.h"
-#include <mutex>
+#include <type_traits>
 
 #define LDS_AS __attribute__((address_space(3)))
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -1223,6 +1223,66 @@ int check_common(int B, int H, int Nq, int Nk, int hd, const long long* strides,
     return 0;
 }
 
+// the fields every entry point fills alike (AttnArgs, TiledArgs): q, k, v, the geometry, the scale and the strides st[0 .. n), in the
+// order {q, k, v, o} x {batch, row} of the forwards (n = 8), then {dq, dk, dv} x {batch, row} of the backwards (n = 14)
+template <class A>
+void fill_common(A& a, const void* q, const void* k, const void* v, int B, int H, int Nq, int Nk, const long long* st, int n, float scale) {
+    a.q = (decltype(a.q))q; a.k = (decltype(a.k))k; a.v = (decltype(a.v))v;
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk;
+    a.q_sb = st[0]; a.q_sr = st[1]; a.k_sb = st[2]; a.k_sr = st[3]; a.v_sb = st[4]; a.v_sr = st[5]; a.o_sb = st[6]; a.o_sr = st[7];
+    if (n == 14) { a.dq_sb = st[8]; a.dq_sr = st[9]; a.dk_sb = st[10]; a.dk_sr = st[11]; a.dv_sb = st[12]; a.dv_sr = st[13]; }
+    a.scale = scale;
+}
+
+// f(HD, MODE) with head_dim 32 | 64 and mode 0 .. 3 (see attn_fwd_impl) as integral constants
+template <int V> using ic = std::integral_constant<int, V>;
+template <class F>
+int by_hd_mode(int hd, int mode, F f) {
+    auto by_mode = [&](auto HD) {
+        switch (mode) {
+            case 1: return f(HD, ic<1>{});
+            case 2: return f(HD, ic<2>{});
+            case 3: return f(HD, ic<3>{});
+            default: return f(HD, ic<0>{});
+        }
+    };
+    return hd == 64 ? by_mode(ic<64>{}) : by_mode(ic<32>{});
+}
+
+// NT = key tiles held in registers per query block: 4 (<= 128 keys), 7 (<= 224: the 196-token decoder grids; one 16-register
+// score tile less than NT = 8 is what lets two waves per SIMD fit) or 8
+template <int HD, int MODE>
+int launch_fwd(const AttnArgs& a, size_t lds, hipStream_t st) {
+    const dim3 grid(a.B * a.H), block(256);
+    const char* what = "attn_fwd";
+    if (a.nkp <= 128) return mmae_launch_lds<attn_fwd_kernel<HD, 4, MODE>>(grid, block, lds, st, what, a);
+    if constexpr (HD == 32 && (MODE == 0 || MODE == 3)) {                // (grouped form at head_dim 64: 168 VGPRs + scratch)
+        static const int env_grp = mmae_env_int("MMAE_ATTN_FWD_GRP", 1);    // 0: all key tiles of a query block in registers at once (A/B)
+        if (env_grp) return mmae_launch_lds<attn_fwd_kernel<HD, 4, MODE, true>>(grid, block, lds, st, what, a);
+    }
+    if (a.nkp <= 224) return mmae_launch_lds<attn_fwd_kernel<HD, 7, MODE>>(grid, block, lds, st, what, a);
+    return mmae_launch_lds<attn_fwd_kernel<HD, 8, MODE>>(grid, block, lds, st, what, a);
+}
+
+template <int HD, int MODE>
+int launch_bwd(const AttnArgs& a, size_t lds, hipStream_t st) {
+    const dim3 grid(a.B * a.H);
+    const char* what = "attn_bwd";
+    const bool twice = lds <= 80 * 1024;                   // two workgroups fit a compute unit: the four-wave forms
+    // RS, the register-resident pass 1 where the keys fit four tiles: 16-bit activations; at head_dim 32 (the output adapters' cross-attention:
+    // 196 queries x 99 keys) since round 6: one evaluation of S / dP and the exponentials less -- the separate delta sweep was a third of the
+    // kernel's v_exp work
+    if constexpr (MODE == 0 || (MODE == 3 && HD == 32)) {
+        static const int env_rs = mmae_env_int("MMAE_ATTN_BWD_RS", 1);      // 0: the separate delta sweep everywhere (A/B)
+        static const int env_rs32 = MODE == 0 && HD == 32 ? mmae_env_int("MMAE_ATTN_BWD_RS32", 1) : 1;
+        if (env_rs && env_rs32 && a.nkp <= 128 && twice) return mmae_launch_lds<attn_bwd_kernel<HD, MODE, 4, true>>(grid, dim3(256), lds, st, what, a);
+    }
+    if constexpr (HD == 64 && MODE != 1) {
+        if (twice) return mmae_launch_lds<attn_bwd_kernel<HD, MODE, 4>>(grid, dim3(256), lds, st, what, a);
+    }
+    return mmae_launch_lds<attn_bwd_kernel<HD, MODE, 8>>(grid, dim3(512), lds, st, what, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1237,41 +1297,15 @@ static int attn_fwd_impl(int mode, const void* q, const void* k, const void* v, 
     MMAE_REQUIRE(rc == 0, rc == -2 ? "attn: head_dim must be 32 or 64" : (rc == -3 ? "attn: strides must be multiples of 8" : "attn: need 1 <= Nq, Nk <= 256"));
     MMAE_REQUIRE(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)o % 16 == 0), "attn_fwd: unaligned pointer");
     AttnArgs a = {};
-    a.q = q; a.k = k; a.v = v; a.out = o; a.lse = lse;
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.nqp = (Nq + 31) / 32 * 32; a.nkp = (Nk + 31) / 32 * 32;
-    a.q_sb = q_sb; a.q_sr = q_sr; a.k_sb = k_sb; a.k_sr = k_sr; a.v_sb = v_sb; a.v_sr = v_sr; a.o_sb = o_sb; a.o_sr = o_sr;
-    a.scale = scale;
+    fill_common(a, q, k, v, B, H, Nq, Nk, st, 8, scale);
+    a.out = o; a.lse = lse;
+    a.nqp = (Nq + 31) / 32 * 32; a.nkp = (Nk + 31) / 32 * 32;
     if (mx_q) {
         MMAE_REQUIRE(!x3 && mx_scale && o_sr == (int64_t)H * hd && o_sb == (int64_t)Nq * o_sr, "attn_fwd_mx: bf16 output, dense [B * Nq][H * head_dim]");
         a.mx_q = (unsigned char*)mx_q; a.mx_s = (unsigned char*)mx_scale; a.mx_rows = (long long)B * Nq; a.mx_ld = H * hd;
     }
     const size_t lds = (size_t)2 * a.nkp * hd * 2 * (x3 ? 2 : 1);
-    hipStream_t st_ = (hipStream_t)stream;
-    dim3 grid(B * H), block(256);
-#define LAUNCH_FWD(HD, NT, X3, ...)                                                                                                       \
-    do {                                                                                                                                  \
-        hipFuncSetAttribute((const void*)attn_fwd_kernel<HD, NT, X3, ##__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((attn_fwd_kernel<HD, NT, X3, ##__VA_ARGS__>), grid, block, lds, st_, a);                                         \
-    } while (0)
-    static const int env_grp = mmae_env_int("MMAE_ATTN_FWD_GRP", 1);    // 0: all key tiles of a query block in registers at once (A/B)
-    // NT = key tiles held in registers per query block: 4 (<= 128 keys), 7 (<= 224: the 196-token decoder grids; one 16-register
-    // score tile less than NT = 8 is what lets two waves per SIMD fit) or 8
-    const bool small = a.nkp <= 128, mid = a.nkp <= 224;
-    if (mode == 1) {
-        if (hd == 64) { if (small) LAUNCH_FWD(64, 4, 1); else if (mid) LAUNCH_FWD(64, 7, 1); else LAUNCH_FWD(64, 8, 1); }
-        else { if (small) LAUNCH_FWD(32, 4, 1); else if (mid) LAUNCH_FWD(32, 7, 1); else LAUNCH_FWD(32, 8, 1); }
-    } else if (mode == 2) {
-        if (hd == 64) { if (small) LAUNCH_FWD(64, 4, 2); else if (mid) LAUNCH_FWD(64, 7, 2); else LAUNCH_FWD(64, 8, 2); }
-        else { if (small) LAUNCH_FWD(32, 4, 2); else if (mid) LAUNCH_FWD(32, 7, 2); else LAUNCH_FWD(32, 8, 2); }
-    } else if (mode == 3) {
-        if (hd == 64) { if (small) LAUNCH_FWD(64, 4, 3); else if (mid) LAUNCH_FWD(64, 7, 3); else LAUNCH_FWD(64, 8, 3); }      // (grouped form at head_dim 64: 168 VGPRs + scratch)
-        else { if (small) LAUNCH_FWD(32, 4, 3); else if (env_grp) LAUNCH_FWD(32, 4, 3, true); else if (mid) LAUNCH_FWD(32, 7, 3); else LAUNCH_FWD(32, 8, 3); }
-    } else {
-        if (hd == 64) { if (small) LAUNCH_FWD(64, 4, 0); else if (mid) LAUNCH_FWD(64, 7, 0); else LAUNCH_FWD(64, 8, 0); }      // (grouped form at head_dim 64: 168 VGPRs + scratch)
-        else { if (small) LAUNCH_FWD(32, 4, 0); else if (env_grp) LAUNCH_FWD(32, 4, 0, true); else if (mid) LAUNCH_FWD(32, 7, 0); else LAUNCH_FWD(32, 8, 0); }
-    }
-#undef LAUNCH_FWD
-    return mmae_check_launch("attn_fwd");
+    return by_hd_mode(hd, mode, [&](auto HD, auto MODE) { return launch_fwd<decltype(HD)::value, decltype(MODE)::value>(a, lds, (hipStream_t)stream); });
 }
 
 static int attn_bwd_impl(int mode, const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, void* dq,
@@ -1286,12 +1320,9 @@ static int attn_bwd_impl(int mode, const void* q, const void* k, const void* v, 
     const int rc = check_common(B, H, Nq, Nk, hd, st, 14);
     MMAE_REQUIRE(rc == 0, rc == -2 ? "attn: head_dim must be 32 or 64" : (rc == -3 ? "attn: strides must be multiples of 8" : "attn: need 1 <= Nq, Nk <= 256"));
     AttnArgs a = {};
-    a.q = q; a.k = k; a.v = v; a.o = o; a.d_o = d_o;
-    a.dq = dq; a.dk = dk; a.dv = dv; a.lse = (float*)lse;
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.nqp = (Nq + 31) / 32 * 32; a.nkp = (Nk + 31) / 32 * 32;
-    a.q_sb = q_sb; a.q_sr = q_sr; a.k_sb = k_sb; a.k_sr = k_sr; a.v_sb = v_sb; a.v_sr = v_sr; a.o_sb = o_sb; a.o_sr = o_sr;
-    a.dq_sb = dq_sb; a.dq_sr = dq_sr; a.dk_sb = dk_sb; a.dk_sr = dk_sr; a.dv_sb = dv_sb; a.dv_sr = dv_sr;
-    a.scale = scale;
+    fill_common(a, q, k, v, B, H, Nq, Nk, st, 14, scale);
+    a.o = o; a.d_o = d_o; a.dq = dq; a.dk = dk; a.dv = dv; a.lse = (float*)lse;
+    a.nqp = (Nq + 31) / 32 * 32; a.nkp = (Nk + 31) / 32 * 32;
     a.dy_amax = dy_amax;
     if (mx_q) {                                           // self-attention with dq | dk | dv packed in one [B * N][3 * H * head_dim] tensor
         const int64_t Dm = (int64_t)H * hd;
@@ -1301,29 +1332,9 @@ static int attn_bwd_impl(int mode, const void* q, const void* k, const void* v, 
         a.mx_q = (unsigned char*)mx_q; a.mx_s = (unsigned char*)mx_scale; a.mx_rows = (long long)B * Nq; a.mx_ld = (int)(3 * Dm);
         a.mx_col[0] = 0; a.mx_col[1] = (int)Dm; a.mx_col[2] = (int)(2 * Dm);
     }
-    const size_t lds = (size_t)2 * (a.nqp + a.nkp) * hd * 2 * (x3 ? 2 : 1) + (size_t)2 * a.nqp * 4;
-    if (lds > 160 * 1024) { mmae_set_error("attn_bwd: tiles exceed the 160 KB LDS (f32 split path: (Nq + Nk) * head_dim too large)"); return MMAE_ESUPPORT; }
-    hipStream_t st_ = (hipStream_t)stream;
-    dim3 grid(B * H);
-#define LAUNCH_BWD(HD, X3, NW, ...)                                                                                                       \
-    do {                                                                                                                                  \
-        hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, X3, NW, ##__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((attn_bwd_kernel<HD, X3, NW, ##__VA_ARGS__>), grid, dim3(NW * 64), lds, st_, a);                                 \
-    } while (0)
-    static const int env_rs = mmae_env_int("MMAE_ATTN_BWD_RS", 1);      // 0: the separate delta sweep everywhere (A/B)
-    const bool rs = env_rs && a.nkp <= 128 && lds <= 80 * 1024;
-    if (mode == 1) { if (hd == 64) LAUNCH_BWD(64, 1, 8); else LAUNCH_BWD(32, 1, 8); }
-    else if (mode == 2) { if (hd == 64) { if (lds <= 80 * 1024) LAUNCH_BWD(64, 2, 4); else LAUNCH_BWD(64, 2, 8); } else LAUNCH_BWD(32, 2, 8); }
-    else if (mode == 3) { if (hd == 64) { if (lds <= 80 * 1024) LAUNCH_BWD(64, 3, 4); else LAUNCH_BWD(64, 3, 8); } else if (rs) LAUNCH_BWD(32, 3, 4, true); else LAUNCH_BWD(32, 3, 8); }
-    else if (hd == 64) { if (rs) LAUNCH_BWD(64, 0, 4, true); else if (lds <= 80 * 1024) LAUNCH_BWD(64, 0, 4); else LAUNCH_BWD(64, 0, 8); }
-    else {
-        // head_dim 32 (the output adapters' cross-attention: 196 queries x 99 keys): the register-resident pass 1 too where the keys fit four tiles
-        // (round 6: one evaluation of S / dP and the exponentials less -- the separate delta sweep was a third of the kernel's v_exp work)
-        static const int env_rs32 = mmae_env_int("MMAE_ATTN_BWD_RS32", 1);
-        if (rs && env_rs32) LAUNCH_BWD(32, 0, 4, true); else LAUNCH_BWD(32, 0, 8);
-    }
-#undef LAUNCH_BWD
-    return mmae_check_launch("attn_bwd");
+    // (f32 split path: (Nq + Nk) * head_dim can exceed the LDS -- the launch then refuses with MMAE_ESUPPORT)
+    const size_t lds = mmae_attn_bwd_lds_bytes(mode, Nq, Nk, hd);
+    return by_hd_mode(hd, mode, [&](auto HD, auto MODE) { return launch_bwd<decltype(HD)::value, decltype(MODE)::value>(a, lds, (hipStream_t)stream); });
 }
 
 
@@ -1339,10 +1350,7 @@ int mmae_xattn_fwd_fused(const void* qn, const void* cn, const void* wq, const f
     XAttnArgs a = {(const uint16_t*)qn, (const uint16_t*)cn, (const uint16_t*)wq, (const uint16_t*)wkv, bq, bkv, (uint16_t*)q, (uint16_t*)kv, (uint16_t*)out, lse,
                    B, H, Nq, Nk, scale};
     const size_t lds = (size_t)128 * 256 * 2;
-    static std::once_flag once;
-    std::call_once(once, [&] { (void)hipFuncSetAttribute((const void*)xattn_fwd_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-    hipLaunchKernelGGL(xattn_fwd_fused_kernel, dim3(B * H), dim3(256), lds, (hipStream_t)stream, a);
-    return mmae_check_launch("xattn_fwd_fused");
+    return mmae_launch_lds<xattn_fwd_fused_kernel>(dim3(B * H), dim3(256), lds, (hipStream_t)stream, "xattn_fwd_fused", a);
 }
 
 int mmae_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int hd,
@@ -1424,20 +1432,13 @@ int mmae_attn_fwd_tiled(const void* q, const void* k, const void* v, void* o, fl
     MMAE_REQUIRE(rc == 0, tiled_msg(rc));
     MMAE_REQUIRE(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)o % 16 == 0), "attn_fwd_tiled: unaligned pointer");
     TiledArgs a = {};
-    a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.out = (uint16_t*)o; a.lse = lse;
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk;
-    a.q_sb = q_sb; a.q_sr = q_sr; a.k_sb = k_sb; a.k_sr = k_sr; a.v_sb = v_sb; a.v_sr = v_sr; a.o_sb = o_sb; a.o_sr = o_sr;
-    a.scale = scale;
+    fill_common(a, q, k, v, B, H, Nq, Nk, st, 8, scale);
+    a.out = (uint16_t*)o; a.lse = lse;
     const size_t lds = (size_t)4 * TROWS * hd * 2;
-    const dim3 grid((unsigned)(B * H * ((Nq + TROWS - 1) / TROWS)));
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)attn_fwd_tiled_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 64 * 2);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_tiled_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 32 * 2);
-    });
-    if (hd == 64) hipLaunchKernelGGL(attn_fwd_tiled_kernel<64>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(attn_fwd_tiled_kernel<32>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    return mmae_check_launch("attn_fwd_tiled");
+    const dim3 grid((unsigned)(B * H * ((Nq + TROWS - 1) / TROWS))), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    const char* what = "attn_fwd_tiled";
+    return hd == 64 ? mmae_launch_lds<attn_fwd_tiled_kernel<64>>(grid, block, lds, s, what, a) : mmae_launch_lds<attn_fwd_tiled_kernel<32>>(grid, block, lds, s, what, a);
 }
 
 /* Backward of mmae_attn_fwd_tiled: two launches (dq, which also writes delta; then dk / dv, which reads it).  o is accepted for symmetry with
@@ -1453,28 +1454,17 @@ int mmae_attn_bwd_tiled(const void* q, const void* k, const void* v, const void*
     MMAE_REQUIRE(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)d_o % 16 == 0), "attn_bwd_tiled: unaligned pointer");
     MMAE_REQUIRE(((uintptr_t)dq % 16 == 0) && ((uintptr_t)dk % 16 == 0) && ((uintptr_t)dv % 16 == 0), "attn_bwd_tiled: unaligned output pointer");
     TiledArgs a = {};
-    a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.d_o = (const uint16_t*)d_o;
-    a.dq = (uint16_t*)dq; a.dk = (uint16_t*)dk; a.dv = (uint16_t*)dv; a.lse = (float*)lse; a.delta = delta;
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk;
-    a.q_sb = q_sb; a.q_sr = q_sr; a.k_sb = k_sb; a.k_sr = k_sr; a.v_sb = v_sb; a.v_sr = v_sr; a.o_sb = o_sb; a.o_sr = o_sr;
-    a.dq_sb = dq_sb; a.dq_sr = dq_sr; a.dk_sb = dk_sb; a.dk_sr = dk_sr; a.dv_sb = dv_sb; a.dv_sr = dv_sr;
-    a.scale = scale;
+    fill_common(a, q, k, v, B, H, Nq, Nk, st, 14, scale);
+    a.d_o = (const uint16_t*)d_o; a.dq = (uint16_t*)dq; a.dk = (uint16_t*)dk; a.dv = (uint16_t*)dv; a.lse = (float*)lse; a.delta = delta;
     const size_t lds_q = (size_t)4 * TROWS * hd * 2, lds_k = lds_q + (size_t)4 * TROWS * 4;
-    const dim3 grid_q((unsigned)(B * H * ((Nq + TROWS - 1) / TROWS))), grid_k((unsigned)(B * H * ((Nk + TROWS - 1) / TROWS)));
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_dq_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 64 * 2);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_dq_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 32 * 2);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_dkdv_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 64 * 2 + 4 * TROWS * 4);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_tiled_dkdv_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TROWS * 32 * 2 + 4 * TROWS * 4);
-    });
-    if (hd == 64) hipLaunchKernelGGL(attn_bwd_tiled_dq_kernel<64>, grid_q, dim3(256), lds_q, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(attn_bwd_tiled_dq_kernel<32>, grid_q, dim3(256), lds_q, (hipStream_t)stream, a);
-    int rl = mmae_check_launch("attn_bwd_tiled (dq)");
+    const dim3 grid_q((unsigned)(B * H * ((Nq + TROWS - 1) / TROWS))), grid_k((unsigned)(B * H * ((Nk + TROWS - 1) / TROWS))), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    const char *what_q = "attn_bwd_tiled (dq)", *what_k = "attn_bwd_tiled (dk, dv)";
+    const int rl = hd == 64 ? mmae_launch_lds<attn_bwd_tiled_dq_kernel<64>>(grid_q, block, lds_q, s, what_q, a)
+                            : mmae_launch_lds<attn_bwd_tiled_dq_kernel<32>>(grid_q, block, lds_q, s, what_q, a);
     if (rl) return rl;
-    if (hd == 64) hipLaunchKernelGGL(attn_bwd_tiled_dkdv_kernel<64>, grid_k, dim3(256), lds_k, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(attn_bwd_tiled_dkdv_kernel<32>, grid_k, dim3(256), lds_k, (hipStream_t)stream, a);
-    return mmae_check_launch("attn_bwd_tiled (dk, dv)");
+    return hd == 64 ? mmae_launch_lds<attn_bwd_tiled_dkdv_kernel<64>>(grid_k, block, lds_k, s, what_k, a)
+                    : mmae_launch_lds<attn_bwd_tiled_dkdv_kernel<32>>(grid_k, block, lds_k, s, what_k, a);
 }
 
 }  // extern "C"

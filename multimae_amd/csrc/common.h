@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "../../include/mmae.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -34,6 +35,39 @@ static inline int mmae_env_int(const char* name, int dflt) {
 #endif
 }
 int mmae_gemm_ex(const mmae_gemm_desc* d, void* stream, int timing_cls, double flop_scale);   // runtime.hip
+
+// ---- launches that ask for dynamic LDS ---------------------------------------------------------------------------------------------
+// A kernel may use more than the default 64 KiB only after hipFuncAttributeMaxDynamicSharedMemorySize was raised for it ON THE DEVICE
+// IT RUNS ON.  mmae_launch_lds is the one place that does so: every launch with dynamic LDS goes through it, launches without any stay
+// plain hipLaunchKernelGGL.  The bytes granted so far are kept per kernel (the template parameter: static storage of the instantiation,
+// no registry) and per device, so that after a kernel's first launch on a device the opt-in costs hipGetDevice and one atomic load.
+constexpr size_t MMAE_LDS_BYTES = 160 * 1024;                 // LDS of one gfx950 compute unit: the most a workgroup can be given
+constexpr int MMAE_MAX_DEVICES = 64;                          // size of the per-device tables (mmae_cu_count, mmae_launch_lds)
+// runtime.hip, the first-launch path: refuses lds > MMAE_LDS_BYTES before any HIP call, else raises the limit of `kernel` on the current
+// device to lds (never lowers it; serialised, so concurrent streams' threads cannot undo each other) and notes it in granted[device].
+// 0, or MMAE_ESUPPORT with the error text set (it names `what` and the bytes) and HIP's last-error state cleared.
+int mmae_lds_opt_in(const void* kernel, std::atomic<int>* granted, size_t lds, const char* what);
+
+template <auto Kernel, typename... Args>
+int mmae_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const char* what, const Args&... args) {
+    static std::atomic<int> granted[MMAE_MAX_DEVICES];       // bytes this kernel has been granted, per device
+    int dev = -1;                                             // (acquire pairs with the opt-in's release store; a plain load on x86-64)
+    if (lds > MMAE_LDS_BYTES || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MMAE_MAX_DEVICES ||
+        (int)lds > granted[dev].load(std::memory_order_acquire)) {
+        const int rc = mmae_lds_opt_in((const void*)Kernel, granted, lds, what);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+    return mmae_check_launch(what);
+}
+
+// Dynamic LDS of the fused attention backward (attention.hip, attn_bwd_kernel): the Q, dO and the K, V tiles over the 32-padded row
+// counts, 16-bit elements -- hi and lo parts of each in mode 1 (f32 activations, split-bf16 products) -- plus the lse and delta rows.
+// ops.py restates the mode 1 figure (_attn_bwd_f32_fits).
+static inline size_t mmae_attn_bwd_lds_bytes(int mode, int Nq, int Nk, int hd) {
+    const size_t nqp = (size_t)(Nq + 31) / 32 * 32, nkp = (size_t)(Nk + 31) / 32 * 32;
+    return 2 * (nqp + nkp) * hd * 2 * (mode == 1 ? 2 : 1) + 2 * nqp * 4;
+}
 
 // query_norm / context_norm outputs of the fused decoder build (tokens.hip: decoder_build_kernel<.., true>; composite.hip: mmae_adapter_fwd)
 struct BuildLn { const float *qg, *qb, *cg, *cb; void *qn, *cn; float *qmean, *qrstd, *cmean, *crstd; float eps; };

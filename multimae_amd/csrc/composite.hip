@@ -969,10 +969,8 @@ int check_adapter(const mmae_adapter_desc* d) {
     }
     const int hd = d->D / d->heads;
     if ((hd != 32 && hd != 64) || d->n_q > 256 || d->NC > 256) { mmae_set_error("adapter: geometry outside the fused attention kernel"); return MMAE_ESUPPORT; }
-    if (d->act_dtype == MMAE_F32) {
-        const int64_t qp = (d->n_q + 31) / 32 * 32, kp = (d->NC + 31) / 32 * 32;
-        if (4 * (qp + kp) * hd * 2 + 8 * qp > 160 * 1024) { mmae_set_error("adapter: f32 attention tiles exceed the LDS"); return MMAE_ESUPPORT; }
-    }
+    // (the split-bf16 footprint for either f32 product mode, as ops.adapter_composite_ok has it)
+    if (d->act_dtype == MMAE_F32 && mmae_attn_bwd_lds_bytes(1, d->n_q, d->NC, hd) > MMAE_LDS_BYTES) { mmae_set_error("adapter: f32 attention tiles exceed the LDS"); return MMAE_ESUPPORT; }
     if ((d->D % 8) || (d->Denc % 8) || (d->Hd % 8) || (kp_of(d) % 4)) { mmae_set_error("adapter: widths must be multiples of 8 (patch row of 4)"); return MMAE_ESUPPORT; }
     MMAE_REQUIRE(d->task_offsets_host && d->w && d->p && d->mask_token && d->task_emb && d->pos && d->enc && d->ids_keep && d->ids_restore && d->act,
                  "adapter: null pointer");

@@ -17,7 +17,6 @@
 // of 32 columns: its weight fragments are K-contiguous 16-byte pieces read straight from L2 into registers, prefetched one
 // unit (4 or 2 k-steps) ahead -- the weight stream (all tasks' weights once per image, ~3 MB for ViT-B) is what bounds the
 // kernel (L2 -> CU at 64 B / clk), the MFMA work is about as long, the pixel gather hides behind both.
-#include <mutex>
 #include <type_traits>
 #include "common.h"
 
@@ -329,7 +328,7 @@ int check_geometry(const mmae_patch_src* srcs, int T, int n_sel, int D) {
         if (k % kq || s.k_off % 8) return 0;
         if (s.kind == 1 && (s.ph * s.pw > MAX_PP || s.n_cls <= 0 || s.n_cls > 32767)) return 0;
     }
-    return lds_bytes(srcs, T, D) + 3 * 1024 <= 160 * 1024;     // + the static arrays
+    return lds_bytes(srcs, T, D) + 3 * 1024 <= MMAE_LDS_BYTES;     // + the static arrays
 }
 
 }  // namespace
@@ -367,14 +366,8 @@ int mmae_patch_embed_fwd(const mmae_patch_src* srcs_host, const void* const* w_b
     a.T = T; a.B = B; a.n_sel = n_sel; a.G = G; a.D = D; a.Ktot = Ktot;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = lds_bytes(srcs_host, T, D);
-    static std::once_flag attr_once;
-    std::call_once(attr_once, [] {
-        (void)hipFuncSetAttribute((const void*)patch_embed_kernel<3, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 3 * 1024);
-        (void)hipFuncSetAttribute((const void*)patch_embed_kernel<4, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 3 * 1024);
-    });
-    if (D <= 768) hipLaunchKernelGGL((patch_embed_kernel<3, 128>), dim3(B), dim3(512), lds, st, a);
-    else hipLaunchKernelGGL((patch_embed_kernel<4, 64>), dim3(B), dim3(512), lds, st, a);
-    return mmae_check_launch("patch_embed_fwd");
+    if (D <= 768) return mmae_launch_lds<patch_embed_kernel<3, 128>>(dim3(B), dim3(512), lds, st, "patch_embed_fwd", a);
+    return mmae_launch_lds<patch_embed_kernel<4, 64>>(dim3(B), dim3(512), lds, st, "patch_embed_fwd", a);
 }
 
 }  // extern "C"

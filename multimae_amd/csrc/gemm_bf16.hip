@@ -10,7 +10,6 @@
 //    gfx950 transposing LDS read ds_read_b64_tr_b16.
 //  * the MFMA is issued as D[n][m] so that a lane owns 4 consecutive n of one row m.
 #include <stdlib.h>
-#include <mutex>
 #include "gemm_common.h"
 
 #define LDS_AS __attribute__((address_space(3)))
@@ -232,12 +231,7 @@ int launch(const GemmArgs& g, int batch, hipStream_t st) {
     a.tiles_n = (g.N + BN - 1) / BN;
     dim3 grid(tiles_m * a.tiles_n, batch, a.splitk), block(WM * WN * 64);
     const size_t lds = 2 * (BM + BN) * 128;
-    static std::once_flag attr_once;
-    std::call_once(attr_once, [&] {
-        hipFuncSetAttribute((const void*)gemm_bf16_kernel<WM, WN, AKS, BKS, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    hipLaunchKernelGGL((gemm_bf16_kernel<WM, WN, AKS, BKS, DMA>), grid, block, lds, st, a);
-    return mmae_check_launch("gemm_bf16");
+    return mmae_launch_lds<gemm_bf16_kernel<WM, WN, AKS, BKS, DMA>>(grid, block, lds, st, "gemm_bf16", a);
 }
 
 template <int WM, int WN, bool DMA>

@@ -2,7 +2,6 @@
 // weight-gradient kernel.  The kernel body lives in gemm_pp_body.h; gemm_bf16_pp_fl.hip holds the instantiations with the
 // epilogue flavour fixed at compile time.
 #include "gemm_pp_body.h"
-#include <mutex>
 
 namespace {
 
@@ -222,14 +221,6 @@ extern "C" int mmae_gemm_dw_group(const mmae_dw_group_desc* d, void* stream) {
     ga.xcd = env_xcd;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)4 * (256 + 256) * 64 + 1024;
-    static std::once_flag attr_once;
-    std::call_once(attr_once, [&] {
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_pp_dwgroup_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_pp_dwgroup_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_pp_dwgroup_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_pp_dwgroup_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_pp_dwgroup_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
 #ifdef MMAE_NO_KF
     static const int env_kf = 0;
 #else
@@ -242,14 +233,14 @@ extern "C" int mmae_gemm_dw_group(const mmae_dw_group_desc* d, void* stream) {
     }
     hipEvent_t t_ev = mmae_timing_begin(st);
     static const int env_wide = mmae_env_int("MMAE_DW_WIDE", 0);      // one phase pair per K tile: measured neutral (421 vs 411-436 us per block), off
-    if (h16) {
-        if (env_kf && (d->rows & 31) == 0) hipLaunchKernelGGL((gemm_bf16_pp_dwgroup_kernel<true, false, true>), dim3(tb, 1, s), dim3(512), lds, st, ga);
-        else hipLaunchKernelGGL((gemm_bf16_pp_dwgroup_kernel<false, false, true>), dim3(tb, 1, s), dim3(512), lds, st, ga);
-    } else
-    if (env_kf && env_wide && (d->rows & 31) == 0) hipLaunchKernelGGL((gemm_bf16_pp_dwgroup_kernel<true, true>), dim3(tb, 1, s), dim3(512), lds, st, ga);
-    else if (env_kf && (d->rows & 31) == 0) hipLaunchKernelGGL(gemm_bf16_pp_dwgroup_kernel<true>, dim3(tb, 1, s), dim3(512), lds, st, ga);
-    else hipLaunchKernelGGL(gemm_bf16_pp_dwgroup_kernel<false>, dim3(tb, 1, s), dim3(512), lds, st, ga);
-    int rc = mmae_check_launch("gemm_bf16_pp_dwgroup");
+    const dim3 grid(tb, 1, s), block(512);
+    const char* what = "gemm_bf16_pp_dwgroup";
+    const bool kf = env_kf && (d->rows & 31) == 0;
+    const int rc = h16 ? (kf ? mmae_launch_lds<gemm_bf16_pp_dwgroup_kernel<true, false, true>>(grid, block, lds, st, what, ga)
+                             : mmae_launch_lds<gemm_bf16_pp_dwgroup_kernel<false, false, true>>(grid, block, lds, st, what, ga))
+                 : kf && env_wide ? mmae_launch_lds<gemm_bf16_pp_dwgroup_kernel<true, true>>(grid, block, lds, st, what, ga)
+                 : kf ? mmae_launch_lds<gemm_bf16_pp_dwgroup_kernel<true>>(grid, block, lds, st, what, ga)
+                      : mmae_launch_lds<gemm_bf16_pp_dwgroup_kernel<false>>(grid, block, lds, st, what, ga);
     if (rc) { mmae_timing_end(t_ev, st, flop, h16 ? 1 : 0, abytes); return rc; }
     hipLaunchKernelGGL(dw_group_reduce_kernel, dim3((unsigned)(rblk < 1 ? 1 : rblk)), dim3(256), 0, st, ra);
     mmae_timing_end(t_ev, st, flop, h16 ? 1 : 0, abytes);

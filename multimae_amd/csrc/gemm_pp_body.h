@@ -23,7 +23,6 @@
 // which every wave reaches after b_4t+4, when the last reader (group 1, MEM(2t+1)) has drained its lgkmcnt.
 #pragma once
 #include <stdlib.h>
-#include <mutex>
 #include "gemm_common.h"
 
 #define LDS_AS __attribute__((address_space(3)))
@@ -707,12 +706,7 @@ int launch(const GemmArgs& g, int batch, hipStream_t st) {
     const int gx = (env_persist && a.tiles_total > n_cu) ? n_cu : a.tiles_total;      // one resident workgroup per CU walks the tile list
     dim3 grid(gx, batch, a.splitk), block(512);
     const size_t lds = (size_t)4 * (BM + BN) * 64 + 1024 + (LNE ? (size_t)BM * 4 * 2 * 4 : 0);      // + the row-statistics exchange of the LayerNorm side output
-    static std::once_flag attr_once;
-    std::call_once(attr_once, [&] {
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_pp_kernel<TM, AKS, BKS, FL, KF, H16, LNE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    hipLaunchKernelGGL((gemm_bf16_pp_kernel<TM, AKS, BKS, FL, KF, H16, LNE>), grid, block, lds, st, a);
-    return mmae_check_launch("gemm_bf16_pp");
+    return mmae_launch_lds<gemm_bf16_pp_kernel<TM, AKS, BKS, FL, KF, H16, LNE>>(grid, block, lds, st, "gemm_bf16_pp", a);
 }
 
 }  // namespace

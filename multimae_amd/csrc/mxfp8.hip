@@ -17,7 +17,6 @@
 // of 64 BYTES per row as before -- now 64 elements: the LDS images, DMA pieces and their counted waits are byte-identical; a
 // wave's two half-phases per K tile split its (TM x 2) scaled MFMAs (64 cycles each) by output rows instead of by K slice.
 #include <stdlib.h>
-#include <mutex>
 #include <type_traits>
 #include "gemm_common.h"
 
@@ -506,12 +505,7 @@ int launch_mx(const GemmArgs& g, hipStream_t st) {
     const long long nv = (long long)a.tiles_total * (a.splitk > 1 ? a.splitk : 1);
     const int gx = nv > n_cu ? n_cu : (int)nv;
     const size_t lds = (size_t)4 * (BM + BN) * 64 + 1024;
-    static std::once_flag attr_once;
-    std::call_once(attr_once, [&] {
-        (void)hipFuncSetAttribute((const void*)gemm_mxfp8_kernel<TM, FL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    hipLaunchKernelGGL((gemm_mxfp8_kernel<TM, FL>), dim3(gx), dim3(512), lds, st, a);
-    return mmae_check_launch("gemm_mxfp8");
+    return mmae_launch_lds<gemm_mxfp8_kernel<TM, FL>>(dim3(gx), dim3(512), lds, st, "gemm_mxfp8", a);
 }
 
 template <int TM>

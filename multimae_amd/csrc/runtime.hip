@@ -4,6 +4,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <mutex>
+#include <vector>
 #include "gemm_common.h"
 
 static thread_local char g_err[256] = "";
@@ -14,9 +16,9 @@ void mmae_set_error(const char* msg) {
 }
 
 int mmae_cu_count() {
-    static std::atomic<int> cached[64];
+    static std::atomic<int> cached[MMAE_MAX_DEVICES];
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MMAE_MAX_DEVICES) return 256;
     int n = cached[dev].load(std::memory_order_relaxed);
     if (n > 0) return n;
     n = 256;
@@ -67,6 +69,28 @@ int mmae_check_launch(const char* what) {
     return 0;
 }
 
+// first-launch path of mmae_launch_lds (common.h)
+int mmae_lds_opt_in(const void* kernel, std::atomic<int>* granted, size_t lds, const char* what) {
+    if (lds > MMAE_LDS_BYTES) {
+        snprintf(g_err, sizeof(g_err), "%s: %zu bytes of dynamic LDS requested, a compute unit has %zu", what, lds, MMAE_LDS_BYTES);
+        return MMAE_ESUPPORT;
+    }
+    static std::mutex mu;                                 // raise-only: two threads' requests for one kernel must not cross
+    std::lock_guard<std::mutex> lk(mu);
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    const bool tabled = e == hipSuccess && dev >= 0 && dev < MMAE_MAX_DEVICES;      // a device beyond the table is opted in at every launch
+    if (tabled && (int)lds <= granted[dev].load(std::memory_order_relaxed)) return 0;
+    if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "%s: cannot opt in to %zu bytes of dynamic LDS: %s", what, lds, hipGetErrorString(e));
+        (void)hipGetLastError();                          // the failure is reported here: it must not colour a later call's check
+        return MMAE_ESUPPORT;
+    }
+    if (tabled) granted[dev].store((int)lds, std::memory_order_release);
+    return 0;
+}
+
 int mmae_gemm_bf16_impl(const mmae_gemm_desc* d, const GemmArgs& g, int code, hipStream_t st);
 int mmae_gemm_bf16_pp_impl(const mmae_gemm_desc* d, const GemmArgs& g, int code, hipStream_t st);
 int mmae_gemm_f32_impl(const mmae_gemm_desc* d, const GemmArgs& g, hipStream_t st);
@@ -76,8 +100,6 @@ int mmae_splitk_reduce(const float* ws, float* C, int M, int N, long long ldc, i
 int mmae_acs_reduce(const float* part, int splits, int M, float* out, int accumulate, hipStream_t st);
 
 // ---- optional launch timing (mmae_gemm_timing_*) ----------------------------------------------------------------------
-#include <mutex>
-#include <vector>
 namespace {
 struct TimedLaunch { hipEvent_t a, b; double flop; int cls; double bytes; };
 std::mutex g_tmu;

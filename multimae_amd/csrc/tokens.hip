@@ -696,29 +696,23 @@ int mmae_semseg_emb_bwd(const void* d_rows, int rows_dtype, int64_t ld, const in
                         int B, int H, int W, int E, int ph, int pw, int n_sel, int k_off, int tok_off, int n_patches, int n_cls,
                         void* stream) {
     MMAE_REQUIRE(d_rows && cls && sel && d_emb && B > 0 && n_cls > 0 && E > 0, "semseg_emb_bwd: bad argument");
-    MMAE_REQUIRE((size_t)n_cls * E * 4 <= 160 * 1024, "semseg_emb_bwd: embedding table exceeds LDS");
     if (rows_dtype != MMAE_BF16 && rows_dtype != MMAE_F32) { mmae_set_error("semseg_emb_bwd: bf16 / f32 rows"); return MMAE_ESUPPORT; }
     const long long n_rows = (long long)B * n_sel;
     const int grid = (int)(n_rows < 512 ? n_rows : 512);
     const size_t lds = (size_t)n_cls * E * 4;
-    hipStream_t st = (hipStream_t)stream;
-    if (rows_dtype == MMAE_BF16) {
-        hipFuncSetAttribute((const void*)semseg_emb_bwd_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((semseg_emb_bwd_kernel<uint16_t>), dim3(grid), dim3(256), lds, st, (const uint16_t*)d_rows, (long long)ld, (const long long*)cls, (const long long*)sel, d_emb, n_rows, n_sel, H, W, E, ph, pw, k_off, tok_off, n_patches, n_cls);
-    } else {
-        hipFuncSetAttribute((const void*)semseg_emb_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((semseg_emb_bwd_kernel<float>), dim3(grid), dim3(256), lds, st, (const float*)d_rows, (long long)ld, (const long long*)cls, (const long long*)sel, d_emb, n_rows, n_sel, H, W, E, ph, pw, k_off, tok_off, n_patches, n_cls);
-    }
-    return mmae_check_launch("semseg_emb_bwd");
+    hipStream_t st = (hipStream_t)stream;                  // (a table beyond the LDS is refused by the launch)
+    if (rows_dtype == MMAE_BF16)
+        return mmae_launch_lds<semseg_emb_bwd_kernel<uint16_t>>(dim3(grid), dim3(256), lds, st, "semseg_emb_bwd", (const uint16_t*)d_rows, (long long)ld, (const long long*)cls, (const long long*)sel, d_emb, n_rows, n_sel, H, W, E, ph, pw, k_off, tok_off, n_patches, n_cls);
+    return mmae_launch_lds<semseg_emb_bwd_kernel<float>>(dim3(grid), dim3(256), lds, st, "semseg_emb_bwd", (const float*)d_rows, (long long)ld, (const long long*)cls, (const long long*)sel, d_emb, n_rows, n_sel, H, W, E, ph, pw, k_off, tok_off, n_patches, n_cls);
 }
 
 // deterministic form: ws f32 [mmae_semseg_emb_bwd_ws_elems()] scratch; accumulate = 0 stores the gradient (no zero-fill of d_emb needed), 1 adds
 static int semseg_det_geometry(int B, int n_sel, int E, int n_cls, int* nsub_out, int* rows_per_out) {
-    if (E < 1 || E > 256 || n_cls < 1) return -1;
+    if (B <= 0 || n_sel <= 0 || E < 1 || E > 256 || n_cls < 1) return -1;      // (no rows: rows_per would be 0)
     int nsub = 256 / E;
     const long long tab = (long long)n_cls * E * 4;
     while (nsub > 1 && nsub * tab > 150 * 1024) --nsub;
-    if (nsub * tab > 160 * 1024) return -1;
+    if (nsub * tab > (long long)MMAE_LDS_BYTES) return -1;
     const long long n_rows = (long long)B * n_sel;
     int grid = (int)(n_rows < 256 ? n_rows : 256);
     if (grid < 1) grid = 1;
@@ -737,19 +731,17 @@ int mmae_semseg_emb_bwd_det(const void* d_rows, int rows_dtype, int64_t ld, cons
     MMAE_REQUIRE(d_rows && cls && sel && d_emb && ws && B > 0 && n_cls > 0 && E > 0, "semseg_emb_bwd_det: bad argument");
     int nsub, rows_per;
     const int grid = semseg_det_geometry(B, n_sel, E, n_cls, &nsub, &rows_per);
-    if (grid < 0) { mmae_set_error("semseg_emb_bwd_det: embedding table exceeds LDS / E > 256"); return MMAE_ESUPPORT; }
+    if (grid < 0) { mmae_set_error("semseg_emb_bwd_det: embedding table exceeds LDS / E > 256 / no rows"); return MMAE_ESUPPORT; }
     MMAE_REQUIRE(ws_elems >= (int64_t)grid * n_cls * E, "semseg_emb_bwd_det: workspace too small (mmae_semseg_emb_bwd_ws_elems)");
     const long long n_rows = (long long)B * n_sel;
     const size_t lds = (size_t)nsub * n_cls * E * 4;
     hipStream_t st = (hipStream_t)stream;
-    if (rows_dtype == MMAE_BF16) {
-        hipFuncSetAttribute((const void*)semseg_emb_bwd_part_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((semseg_emb_bwd_part_kernel<uint16_t>), dim3(grid), dim3(256), lds, st, (const uint16_t*)d_rows, (long long)ld, (const long long*)cls, (const long long*)sel, ws, n_rows, rows_per, n_sel, H, W, E, ph, pw, k_off, tok_off, n_patches, n_cls, nsub);
-    } else if (rows_dtype == MMAE_F32) {
-        hipFuncSetAttribute((const void*)semseg_emb_bwd_part_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((semseg_emb_bwd_part_kernel<float>), dim3(grid), dim3(256), lds, st, (const float*)d_rows, (long long)ld, (const long long*)cls, (const long long*)sel, ws, n_rows, rows_per, n_sel, H, W, E, ph, pw, k_off, tok_off, n_patches, n_cls, nsub);
-    } else { mmae_set_error("semseg_emb_bwd_det: bf16 / f32 rows"); return MMAE_ESUPPORT; }
-    int rc = mmae_check_launch("semseg_emb_bwd_part");
+    int rc;
+    if (rows_dtype == MMAE_BF16)
+        rc = mmae_launch_lds<semseg_emb_bwd_part_kernel<uint16_t>>(dim3(grid), dim3(256), lds, st, "semseg_emb_bwd_part", (const uint16_t*)d_rows, (long long)ld, (const long long*)cls, (const long long*)sel, ws, n_rows, rows_per, n_sel, H, W, E, ph, pw, k_off, tok_off, n_patches, n_cls, nsub);
+    else if (rows_dtype == MMAE_F32)
+        rc = mmae_launch_lds<semseg_emb_bwd_part_kernel<float>>(dim3(grid), dim3(256), lds, st, "semseg_emb_bwd_part", (const float*)d_rows, (long long)ld, (const long long*)cls, (const long long*)sel, ws, n_rows, rows_per, n_sel, H, W, E, ph, pw, k_off, tok_off, n_patches, n_cls, nsub);
+    else { mmae_set_error("semseg_emb_bwd_det: bf16 / f32 rows"); return MMAE_ESUPPORT; }
     if (rc) return rc;
     const int n = n_cls * E;
     hipLaunchKernelGGL(semseg_emb_bwd_sum_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const float*)ws, d_emb, n, grid, accumulate);

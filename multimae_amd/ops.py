@@ -376,6 +376,15 @@ def stream_workspace(stream_handle: int, device, elems: Optional[int] = None) ->
     return w
 
 
+LDS_BYTES = 160 * 1024                                    # LDS of one compute unit (csrc/common.h: MMAE_LDS_BYTES)
+
+
+def _attn_bwd_f32_fits(Nq: int, Nk: int, hd: int) -> bool:
+    """the fused attention backward's hi / lo tiles of f32 activations fit the LDS: csrc/common.h, mmae_attn_bwd_lds_bytes(1, Nq, Nk, hd)"""
+    qp, kp = round_up(Nq, 32), round_up(Nk, 32)
+    return 4 * (qp + kp) * hd * 2 + 8 * qp <= LDS_BYTES
+
+
 def block_composite_ok(x: Tensor, act: torch.dtype, heads: int, N: int) -> bool:
     D = x.shape[1]
     hd = D // heads
@@ -385,8 +394,7 @@ def block_composite_ok(x: Tensor, act: torch.dtype, heads: int, N: int) -> bool:
         return True
     if N > 256:
         return False
-    lds_bwd = 4 * 2 * round_up(N, 32) * hd * 2 + 8 * round_up(N, 32)
-    return act == torch.float32 and _f32_split() and lds_bwd <= 160 * 1024
+    return act == torch.float32 and _f32_split() and _attn_bwd_f32_fits(N, N, hd)
 
 
 def _block_desc(P: Sequence[Tensor], wts: Sequence[Tensor], heads: int, eps: float, act: torch.dtype, B: int, N: int, D: int) -> 'BlockDesc':
@@ -660,8 +668,7 @@ def adapter_composite_ok(enc: Tensor, act: torch.dtype, heads: int, D: int, n_q:
         return False
     if act == torch.bfloat16:
         return True
-    lds_bwd = 4 * (round_up(n_q, 32) + round_up(NC, 32)) * hd * 2 + 8 * round_up(n_q, 32)
-    return act == torch.float32 and _f32_split() and lds_bwd <= 160 * 1024
+    return act == torch.float32 and _f32_split() and _attn_bwd_f32_fits(n_q, NC, hd)
 
 
 class X3Weights:
@@ -1074,8 +1081,7 @@ def _fusable(q: AttnView, k: AttnView, hd: int) -> bool:
         return True
     # f32 activations: only where the surrounding GEMMs are split-bf16 too (fp32 adapters in speed mode); the backward's
     # eight hi/lo tiles must fit the 160 KB LDS
-    lds_bwd = 4 * (round_up(q.N, 32) + round_up(k.N, 32)) * hd * 2 + 8 * round_up(q.N, 32)
-    return q.t.dtype == torch.float32 and _f32_split() and lds_bwd <= 160 * 1024
+    return q.t.dtype == torch.float32 and _f32_split() and _attn_bwd_f32_fits(q.N, k.N, hd)
 
 
 def _tiled(q: AttnView, k: AttnView) -> bool:

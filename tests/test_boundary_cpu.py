@@ -19,6 +19,35 @@ def test_cabi_exports_every_declared_symbol():
     assert _lib.load().mmae_abi_version() == 7        # load() also checks every ctypes struct mirror against mmae_struct_size()
 
 
+def test_semseg_emb_workspace_query_with_no_rows():
+    """mmae_semseg_emb_bwd_ws_elems is host-only.  Without rows (B = 0 or n_sel = 0) the geometry has no rows per workgroup: -1, 'not
+    supported', where it once divided by that zero.  With rows it still answers workgroups * n_cls * E: at most 256 workgroups, each
+    taking ceil(rows / 256) rows, so ceil(rows / rows_per) of them."""
+    from multimae_amd import _lib
+    lib = _lib.load()
+    assert int(lib.mmae_semseg_emb_bwd_ws_elems(0, 98, 64, 133)) == -1
+    assert int(lib.mmae_semseg_emb_bwd_ws_elems(4, 0, 64, 133)) == -1
+    rows = 4 * 98
+    rows_per = -(-rows // 256)
+    grid = -(-rows // rows_per)
+    assert (rows_per, grid) == (2, 196)
+    assert int(lib.mmae_semseg_emb_bwd_ws_elems(4, 98, 64, 133)) == grid * 133 * 64
+
+
+def test_launch_beyond_the_lds_is_refused_before_any_device_call():
+    """A launch that asks for more dynamic LDS than a compute unit has (160 KiB) is refused by the launch helper itself, before the first
+    HIP call: MMAE_ESUPPORT and a message with the caller's name and the bytes, here without a device in the machine.  The class table of
+    mmae_semseg_emb_bwd is n_cls * E * 4 bytes of LDS: 700 x 64 x 4 = 179200.  (No pointer is read on the host.)"""
+    from multimae_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+    rc = lib.mmae_semseg_emb_bwd(p, _lib.F32, 64, p, p, p, 1, 4, 4, 64, 2, 2, 1, 0, 0, 4, 700, None)
+    assert rc == -3                                    # MMAE_ESUPPORT
+    msg = lib.mmae_last_error().decode()
+    assert 'semseg_emb_bwd' in msg and '179200' in msg, msg
+
+
 def test_state_dict_contract_and_seeded_init_base():
     """Appendix A: 351 keys; same RNG call order as the reference => identical initial weights."""
     gold = load_scalars()['base_rgb_depth_semseg']
