@@ -9,7 +9,11 @@
 and the semantic-segmentation fine-tuning script's import lines (run_finetuning_semseg.py:36-39):
 
     from multimae.output_adapters import (ConvNeXtAdapter, DPTOutputAdapter,
-                                          SegmenterMaskTransformerAdapter)   # DPT / Segmenter: names only, constructing one raises
+                                          SegmenterMaskTransformerAdapter)   # Segmenter: name only, constructing it raises
+
+and the depth and Taskonomy scripts' (run_finetuning_depth.py:39, run_finetuning_taskonomy.py):
+
+    from multimae.output_adapters import ConvNeXtAdapter, DPTOutputAdapter   # the DPT head with head_type='regression'
 
 (reference import surface: run_pretraining_multimae.py:36-40, multimae/__init__.py)."""
 import os

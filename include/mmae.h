@@ -1050,6 +1050,34 @@ int mmae_upsample2x_fwd(const float* x, float* y, int B, int h, int w, int C, vo
 int mmae_upsample2x_bwd(const float* g, float* dx, int B, int h, int w, int C, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The DPT head's regression tail and the weights of its transposed convolutions (DPTOutputAdapter, output_adapters.py:576-759),
+ * csrc/dpt.hip.  No float atomics; results are bit-equal from run to run; no host synchronisation; f32 arithmetic in both
+ * precision modes.
+ *   dpt_tail_fwd:  replaces nn.ReLU(True) -> nn.Conv2d(32, num_channels, 1) (output_adapters.py:631-632) in one pass: x f32
+ *                  channels-last [B][H][W][C], w f32 [K][C], bias f32 [K] -> out f32 NCHW [B][K][H][W],
+ *                  out[b][k][p] = bias[k] + sum_c w[k][c] max(x[b][p][c], 0), c ascending.  x is not modified.
+ *                  C % 4 == 0, 4 <= C <= 64, 1 <= K <= 16 (= MMAE_REG_MAX_K), x and w 16-byte aligned; else MMAE_EINVAL before any launch.
+ *   dpt_tail_bwd:  g f32 [B][K][H][W] and the saved x -> dx f32 [B][H][W][C] = (x > 0) * sum_k g[b][k][p] w[k][c] (k ascending), and
+ *                  part f32 [nblk][K C + K] (nblk = mmae_dpt_tail_bwd_nblk): row j = workgroup j's sums dW[k][c] = sum g max(x, 0)
+ *                  (columns k C + c) and db[k] = sum g (columns K C + k) over its pixels in ascending order; sum the rows with
+ *                  mmae_colsum_partials.  The same geometry limits.
+ *   dpt_tail_bwd_nblk: host only, >= 1 for B H W >= 1.
+ *   deconv_weight_pack: nn.ConvTranspose2d(Cin, Cout, kernel_size=s, stride=s) (output_adapters.py:667-672,681-686) as a row GEMM
+ *                  [rows, Cin] x [Cin, s s Cout] followed by mmae_convnext_shuffle_fwd: the (Cin, Cout, s, s) f32 weight ->
+ *                  wp[(i s + j) Cout + co][ci] in wp_dtype (MMAE_F32 | MMAE_BF16), and bias [Cout] -> bp f32 [s s Cout] (tiled) for the
+ *                  GEMM's bias epilogue; bias and bp may both be NULL.
+ *   deconv_weight_unpack: the way back for the gradients: dw[ci][co][i][j] (+)= dwp[(i s + j) Cout + co][ci] and
+ *                  db[co] (+)= sum_(i, j) dbp[(i s + j) Cout + co], the s s terms in index order; all f32; either pair may be NULL.
+ * ------------------------------------------------------------------------- */
+int mmae_dpt_tail_fwd(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int C, int K, void* stream);
+int mmae_dpt_tail_bwd_nblk(int B, int H, int W);
+int mmae_dpt_tail_bwd(const float* g, const float* x, const float* w, float* dx, float* part, int B, int H, int W, int C, int K,
+                      void* stream);
+int mmae_deconv_weight_pack(const float* w, const float* bias, void* wp, int wp_dtype, float* bp, int Cin, int Cout, int s, void* stream);
+int mmae_deconv_weight_unpack(const float* dwp, const float* dbp, float* dw, float* db, int Cin, int Cout, int s, int accumulate,
+                              void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Semantic-segmentation loss and metrics on the head's low-resolution logits, csrc/segloss.hip: the (B, K, H, W) image of
  * mmae_resize_fwd is never read.  x f32 [B][h][w][ldx] (first K columns), target / pred / label int64 [B][H][W], mode as in
  * mmae_resize_fwd (every geometry it takes is taken here), the interpolated value bit-identical to the pixel it would store.  A target

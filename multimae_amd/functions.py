@@ -1711,3 +1711,157 @@ class Upsample2xFn(torch.autograd.Function):
     def backward(ctx, dy: Tensor):
         B, h, w, C = ctx.geom
         return ops.upsample2x_bwd(_nhwc(dy), B, h, w, C).permute(0, 3, 1, 2)
+
+
+# ------------------------------------------------------------------------------------------
+# The DPT head around the fusion blocks (DPTOutputAdapter, output_adapters.py:576-759): the reassembly of one hooked layer and
+# the regression head, on csrc/dpt.hip, csrc/conv3x3.hip, the ConvNeXt head's row gather / pixel shuffle and the engine's GEMMs
+# ------------------------------------------------------------------------------------------
+def _deconv_wgrad(sink: GradSink, w: Tensor, b: Tensor, dwp: Tensor, dbp: Tensor, s: int):
+    """the packed gradients of a transposed convolution into those of its (Cin, Cout, s, s) weight and (Cout,) bias: stored into fresh
+    tensors, or accumulated into the arena"""
+    outs = []
+    for p, pair in ((w, (dwp, None)), (b, (None, dbp))):
+        if not p.requires_grad:
+            outs.append(None)
+            continue
+        tgt, acc = sink._target(p)
+        args = (pair[0], pair[1], tgt if pair[0] is not None else None, tgt if pair[1] is not None else None, s, acc, w.shape[0])
+        if sink.side is not None and acc:
+            sink._on_side(lambda a=args: ops.deconv_weight_unpack(*a), dwp, dbp)
+        else:
+            ops.deconv_weight_unpack(*args)
+        outs.append(None if acc else tgt)
+    return outs
+
+
+class DPTReassembleFn(torch.autograd.Function):
+    """One hooked layer of DPTOutputAdapter.forward (output_adapters.py:736-748) as ONE autograd node: adapt_tokens, the rearrange
+    into a map, act_postprocess[i] and scratch.layer_rn[i].  The main tasks' token rows are gathered side by side into
+    [B N, tasks x D] rows in the activation dtype -- token rows are channels-last pixels already, so this is the rearrange -- and the
+    1 x 1 convolution is a row GEMM.  Then, per layer: i = 0, 1 the transposed convolution (kernel = stride = 4 | 2) as a row GEMM
+    against the packed weight and a pixel shuffle; i = 2 nothing; i = 3 a 3 x 3 convolution of stride 2; and the bias-free 3 x 3
+    convolution of layer_rn[i].  Returns the (B, feature_dim, h_i, w_i)-shaped channels-last strided f32 map.
+    cfg: act, wc, cap, layer, starts, N, NH, NW.  params: act_postprocess[i].0.{weight, bias}, [act_postprocess[i].1.{weight, bias}
+    for i != 2,] layer_rn[i].weight."""
+
+    @staticmethod
+    def forward(ctx, cfg: _Cfg, tokens: Tensor, *params: Tensor):
+        ops._require_gpu(tokens, 'DPTOutputAdapter tokens')
+        act, wc, i = cfg.act, cfg.wc, cfg.layer
+        B, n_tok, D = tokens.shape
+        N, NH, NW = cfg.N, cfg.NH, cfg.NW
+        f32 = torch.float32
+        w1, b1 = params[0], params[1]
+        rn = params[-1]
+        L, TD = w1.shape[0], w1.shape[1]
+        enc = tokens.detach().contiguous().float()
+        x_tok = _new((B * N, TD), enc, act)
+        for t, st in enumerate(cfg.starts):                       # adapt_tokens + torch.cat (:717-726)
+            ops.convnext_rows_gather(enc, x_tok, st, N, t * D)
+        s = {0: 4, 1: 2}.get(i, 1)
+        y1 = ops.linear_fwd(x_tok, wc(w1).view(L, TD), b1.detach(), _new((B * N, L), enc, act if s > 1 else f32))
+        wp2 = None
+        if s > 1:                                                 # nn.ConvTranspose2d(L, L, s, s): row GEMM + pixel shuffle
+            wp2, bp2 = ops.deconv_weight_pack(params[2].detach().contiguous(), params[3].detach().contiguous(), s, act)
+            proj = ops.linear_fwd(y1, wp2, bp2, _new((B * N, s * s * L), enc, f32))
+            m = ops.convnext_shuffle(proj, _new((B, NH * s, NW * s, L), enc, f32), B, NH, NW, s, L)
+            del proj
+        elif i == 3:                                              # nn.Conv2d(L, L, 3, stride=2, padding=1)
+            wp2 = ops.conv3x3_weight_pack(params[2].detach().contiguous(), act)
+            m = conv3x3_fwd(y1.view(B, NH, NW, L), wp2, params[3].detach(), 2, False, None, cfg.cap)
+        else:
+            m = y1.view(B, NH, NW, L)
+        wpr = ops.conv3x3_weight_pack(rn.detach().contiguous(), act)
+        y = conv3x3_fwd(m, wpr, None, 1, False, None, cfg.cap)    # scratch.layer_rn[i]
+        ctx.cfg, ctx.params = cfg, params
+        ctx.saved = (x_tok, y1, wp2, m, wpr, (B, n_tok, D, L, TD, s))
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        cfg, params = ctx.cfg, ctx.params
+        x_tok, y1, wp2, m, wpr, (B, n_tok, D, L, TD, s) = ctx.saved
+        act, wc, i = cfg.act, cfg.wc, cfg.layer
+        N, NH, NW = cfg.N, cfg.NH, cfg.NW
+        f32 = torch.float32
+        sink = GradSink(engine.direct_grads())
+        grads: List[Optional[Tensor]] = [None] * len(params)
+        w1, b1, rn = params[0], params[1], params[-1]
+        g = _nhwc(dy)
+        dm, dwpr = conv3x3_bwd(g, m, wpr, 1, False, None, cfg.cap, True, rn.requires_grad)
+        grads[-1] = _conv_wgrad(sink, rn, dwpr)
+        del g
+        if s > 1:
+            d_proj = ops.convnext_shuffle(dm, _new((B * N, s * s * L), dm, f32), B, NH, NW, s, L, inverse=True)
+            dpa = ops.cast(d_proj, act)
+            del d_proj
+            d_y1 = ops.linear_dx(dpa, wp2, _new((B * N, L), dm, f32))
+            dwp = _new((s * s * L, L), dm, f32)
+            dbp = _new((s * s * L,), dm, f32)
+            ops.linear_dw(dpa, y1, dwp, False, db=dbp)
+            grads[2], grads[3] = _deconv_wgrad(sink, params[2], params[3], dwp, dbp, s)
+        elif i == 3:
+            d_y1, dwp = conv3x3_bwd(dm, y1.view(B, NH, NW, L), wp2, 2, False, None, cfg.cap, True, params[2].requires_grad)
+            grads[2] = _conv_wgrad(sink, params[2], dwp)
+            grads[3] = sink.bias(params[3], dm.view(-1, L))
+        else:
+            d_y1 = dm
+        d1a = ops.cast(d_y1.view(B * N, L), act)
+        d_enc = None
+        if ctx.needs_input_grad[1]:
+            d_tok = ops.linear_dx(d1a, wc(w1).view(L, TD), _new((B * N, TD), d1a, f32))
+            d_enc = torch.zeros((B, n_tok, D), device=d1a.device, dtype=f32)       # global tokens and other tasks' rows: 0
+            for t, st in enumerate(cfg.starts):
+                ops.convnext_rows_scatter(d_tok, d_enc, st, N, t * D)
+        grads[0], grads[1] = sink.linear(w1, b1, d1a, x_tok)
+        ctx.saved = ctx.params = None
+        return (None, d_enc, *grads)
+
+
+class DPTHeadFn(torch.autograd.Function):
+    """The regression head of DPTOutputAdapter (output_adapters.py:627-633) as ONE autograd node: conv3x3 C -> C / 2, bilinear x2
+    (align_corners=True), conv3x3 C / 2 -> 32, then ReLU and the 1 x 1 convolution to K channels in one kernel (mmae_dpt_tail_fwd),
+    which writes the f32 (B, K, H, W) image, contiguous NCHW.  cfg: act, cap.  params: head.0.{weight, bias}, head.2.{weight, bias},
+    head.4.{weight, bias}."""
+
+    @staticmethod
+    def forward(ctx, cfg: _Cfg, x: Tensor, *params: Tensor):
+        ops._require_gpu(x, 'DPTOutputAdapter head input')
+        c1w, c1b, c2w, c2b, tw, tb = params
+        C, Ch, Ct, K = c1w.shape[1], c1w.shape[0], c2w.shape[0], tw.shape[0]
+        _check_map('DPTOutputAdapter head', x, C)
+        _check_conv(cfg, 'DPTOutputAdapter head', C, Ch, Ct)
+        a = _nhwc(x)
+        B, h, w, _ = a.shape
+        wp1 = ops.conv3x3_weight_pack(c1w.detach().contiguous(), cfg.act)
+        wp2 = ops.conv3x3_weight_pack(c2w.detach().contiguous(), cfg.act)
+        t1 = conv3x3_fwd(a, wp1, c1b.detach(), 1, False, None, cfg.cap)
+        up = ops.upsample2x_fwd(t1, B, h, w, Ch)
+        del t1
+        t2 = conv3x3_fwd(up, wp2, c2b.detach(), 1, False, None, cfg.cap)
+        out = ops.dpt_tail_fwd(t2, tw.detach().contiguous().view(K, Ct), tb.detach().contiguous())
+        ctx.cfg, ctx.params = cfg, params
+        ctx.saved = (a, wp1, up, wp2, t2, (B, h, w, Ch, Ct, K))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        cfg, params = ctx.cfg, ctx.params
+        a, wp1, up, wp2, t2, (B, h, w, Ch, Ct, K) = ctx.saved
+        c1w, c1b, c2w, c2b, tw, tb = params
+        sink = GradSink(engine.direct_grads())
+        g = d_out.contiguous().float()
+        dt2, part = ops.dpt_tail_bwd(g, t2, tw.detach().contiguous().view(K, Ct))
+        gt = ops.reduce_partials(part, _new((K * Ct + K,), g, torch.float32), False)      # [dW | db]
+        gtw, gtb = sink.vec(tw, gt[:K * Ct]), sink.vec(tb, gt[K * Ct:])
+        del t2, part
+        dup, dwp2 = conv3x3_bwd(dt2, up, wp2, 1, False, None, cfg.cap, True, c2w.requires_grad)
+        g2w, g2b = _conv_wgrad(sink, c2w, dwp2), sink.bias(c2b, dt2.view(-1, Ct))
+        del dt2
+        dt1 = ops.upsample2x_bwd(dup, B, h, w, Ch)
+        del dup
+        dx, dwp1 = conv3x3_bwd(dt1, a, wp1, 1, False, None, cfg.cap, ctx.needs_input_grad[1], c1w.requires_grad)
+        g1w, g1b = _conv_wgrad(sink, c1w, dwp1), sink.bias(c1b, dt1.view(-1, Ch))
+        ctx.saved = ctx.params = None
+        return (None, (dx.permute(0, 3, 1, 2) if dx is not None else None), g1w, g1b, g2w, g2b, gtw, gtb)

@@ -1620,6 +1620,92 @@ def upsample2x_bwd(g: Tensor, B: int, h: int, w: int, C: int) -> Tensor:
     return dx
 
 
+# ------------------------------------------- the DPT head's regression tail and transposed-convolution weights (csrc/dpt.hip) --
+DPT_TAIL_MAX_K = 16          # == MMAE_REG_MAX_K: accumulators the tail kernel keeps in registers
+
+
+def _check_tail(what: str, x: Tensor, w: Tensor, K: int, C: int) -> None:
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[3] != C or x.numel() == 0:
+        raise ValueError(f'{what}: the map must be a non-empty contiguous f32 [B, H, W, {C}] tensor, got {tuple(x.shape)} {x.dtype}')
+    if C % 4 or not 4 <= C <= 64 or not 1 <= K <= DPT_TAIL_MAX_K:
+        raise ValueError(f'{what}: C = {C} must be a multiple of 4 in [4, 64] and K = {K} in [1, {DPT_TAIL_MAX_K}]')
+    if w.dtype != torch.float32 or not w.is_contiguous() or w.numel() != K * C:
+        raise ValueError(f'{what}: the weight must be a contiguous f32 tensor of {K} x {C} elements, got {tuple(w.shape)} {w.dtype}')
+
+
+def dpt_tail_fwd(x: Tensor, w: Tensor, bias: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """nn.ReLU -> nn.Conv2d(C, K, 1) on the f32 NHWC map x [B, H, W, C]: out f32 NCHW [B, K, H, W] = bias + w . max(x, 0)"""
+    B, H, W, C = x.shape if x.dim() == 4 else (0, 0, 0, 0)
+    K = bias.numel()
+    _check_tail('dpt_tail_fwd', x, w, K, C)
+    if bias.dtype != torch.float32 or not bias.is_contiguous():
+        raise ValueError(f'dpt_tail_fwd: the bias must be a contiguous f32 tensor, got {bias.dtype}')
+    if out is None:
+        out = torch.empty((B, K, H, W), device=x.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or out.numel() != B * K * H * W or not out.is_contiguous():
+        raise ValueError(f'dpt_tail_fwd: the output must be a contiguous f32 tensor of {B * K * H * W} elements')
+    check(_lib.load().mmae_dpt_tail_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, C, K, _stream()), 'dpt_tail_fwd')
+    return out
+
+
+def dpt_tail_bwd(g: Tensor, x: Tensor, w: Tensor, dx: Optional[Tensor] = None):
+    """its backward for g f32 [B, K, H, W]: (dx f32 [B, H, W, C], the UNREDUCED partials f32 [nblk, K C + K] of [dW | db]; reduce with
+    reduce_partials)"""
+    B, H, W, C = x.shape if x.dim() == 4 else (0, 0, 0, 0)
+    K = g.shape[1] if g.dim() == 4 else 0
+    _check_tail('dpt_tail_bwd', x, w, K, C)
+    if g.dtype != torch.float32 or not g.is_contiguous() or tuple(g.shape) != (B, K, H, W):
+        raise ValueError(f'dpt_tail_bwd: the gradient must be a contiguous f32 [{B}, {K}, {H}, {W}] tensor, got {tuple(g.shape)} {g.dtype}')
+    if dx is None:
+        dx = torch.empty_like(x)
+    elif dx.dtype != torch.float32 or dx.numel() != x.numel() or not dx.is_contiguous():
+        raise ValueError(f'dpt_tail_bwd: dx must be a contiguous f32 tensor of {x.numel()} elements')
+    lib = _lib.load()
+    nblk = max(1, int(lib.mmae_dpt_tail_bwd_nblk(B, H, W)))
+    part = torch.empty((nblk, K * C + K), device=x.device, dtype=torch.float32)
+    check(lib.mmae_dpt_tail_bwd(g.data_ptr(), x.data_ptr(), w.data_ptr(), dx.data_ptr(), part.data_ptr(), B, H, W, C, K, _stream()), 'dpt_tail_bwd')
+    return dx, part
+
+
+def _check_deconv(what: str, w: Tensor, s: int):
+    if w.dim() != 4 or w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape[2:]) != (s, s) or not 1 <= s <= 8 or w.numel() == 0:
+        raise ValueError(f'{what}: the weight must be a contiguous f32 (Cin, Cout, {s}, {s}) tensor with 1 <= s <= 8, got {tuple(w.shape)} {w.dtype}')
+    return w.shape[0], w.shape[1]
+
+
+def deconv_weight_pack(w: Tensor, bias: Optional[Tensor], s: int, dtype: torch.dtype):
+    """nn.ConvTranspose2d(kernel_size=s, stride=s)'s (Cin, Cout, s, s) f32 weight -> the [s s Cout, Cin] GEMM operand in (i, j, co) row
+    order, rounded to `dtype`, and its bias tiled to f32 [s s Cout] (None without a bias)"""
+    Cin, Cout = _check_deconv('deconv_weight_pack', w, s)
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != Cout or not bias.is_contiguous()):
+        raise ValueError(f'deconv_weight_pack: the bias must be a contiguous f32 tensor of {Cout} elements')
+    wp = torch.empty((s * s * Cout, Cin), device=w.device, dtype=dtype)
+    bp = torch.empty((s * s * Cout,), device=w.device, dtype=torch.float32) if bias is not None else None
+    check(_lib.load().mmae_deconv_weight_pack(w.data_ptr(), _p(bias), wp.data_ptr(), dcode(dtype), _p(bp), Cin, Cout, s, _stream()),
+          'deconv_weight_pack')
+    return wp, bp
+
+
+def deconv_weight_unpack(dwp: Optional[Tensor], dbp: Optional[Tensor], dw: Optional[Tensor], db: Optional[Tensor], s: int,
+                         accumulate: bool, Cin: Optional[int] = None) -> None:
+    """dw (Cin, Cout, s, s) f32 (+)= the [s s Cout, Cin] gradient in the packed order; db [Cout] (+)= the s s tiles of dbp [s s Cout]
+    summed in index order.  Either pair may be None (Cin must then be given with the bias pair alone)."""
+    if (dwp is None) != (dw is None) or (dbp is None) != (db is None) or (dw is None and db is None):
+        raise ValueError('deconv_weight_unpack: dwp / dw and dbp / db go in pairs, one pair at least')
+    if dw is not None:
+        Cin, Cout = _check_deconv('deconv_weight_unpack', dw, s)
+        if dwp.dtype != torch.float32 or not dwp.is_contiguous() or dwp.numel() != dw.numel():
+            raise ValueError(f'deconv_weight_unpack: the packed gradient must be a contiguous f32 tensor of {dw.numel()} elements')
+    else:
+        Cout = db.numel()
+        Cin = int(Cin or 1)
+    if db is not None and (db.dtype != torch.float32 or db.numel() != Cout or not db.is_contiguous() or dbp.dtype != torch.float32
+                           or not dbp.is_contiguous() or dbp.numel() != s * s * Cout or not 1 <= s <= 8):
+        raise ValueError(f'deconv_weight_unpack: db must hold {Cout} and dbp {s * s * Cout} contiguous f32 elements')
+    check(_lib.load().mmae_deconv_weight_unpack(_p(dwp), _p(dbp), _p(dw), _p(db), Cin, Cout, s, int(accumulate), _stream()),
+          'deconv_weight_unpack')
+
+
 # ------------------------------------------------- segmentation loss and metrics on the low-resolution logits (csrc/segloss.hip) --
 SEG_PARTIALS = 2048          # MMAE_SEG_PARTIALS: rows of the forward's per-workgroup (sum, count) scratch
 SEG_HIST_MAX_K = 4096        # MMAE_SEG_HIST_MAX_K

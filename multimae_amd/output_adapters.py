@@ -11,20 +11,23 @@ reference is never materialised.
 LinearOutputAdapter (output_adapters.py:285-356, the classification head of the MultiViT fine-tuning forward,
 SURVEY.md section 8f row 4) is built on the same kernels.  ConvNeXtAdapter (output_adapters.py:481-573, the default head of
 run_finetuning_semseg.py) is one autograd node (functions.ConvNeXtHeadFn) on the row kernels, the GEMMs and csrc/convnext.hip.
-The other dense-prediction heads (DPTOutputAdapter, SegmenterMaskTransformerAdapter) are not built: their names exist so that
-the semseg script's import line works, and constructing one raises NotImplementedError.
+DPTOutputAdapter (output_adapters.py:576-759, the head of every shipped depth and Taskonomy recipe) is built with the regression head
+type: ten autograd nodes (functions.DPTReassembleFn x 4, the fusion blocks of output_adapter_utils.py, functions.DPTHeadFn) on
+csrc/dpt.hip, csrc/conv3x3.hip and the GEMMs.  SegmenterMaskTransformerAdapter is not built: its name exists so that the semseg
+script's import line works, and constructing it raises NotImplementedError.
 """
 from __future__ import annotations
 
 from functools import partial
-from typing import Dict, Iterable, Optional, Tuple, Union
+from typing import Dict, Iterable, List, Optional, Tuple, Union
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import engine
-from .functions import ConvNeXtHeadFn, SpatialAdapterFn, TokenMeanFn
+from .functions import ConvNeXtHeadFn, DPTHeadFn, DPTReassembleFn, SpatialAdapterFn, TokenMeanFn
+from .output_adapter_utils import Conv3x3, Interpolate, _conv_cfg, make_fusion_block, make_scratch
 from .multimae_utils import (Block, CrossAttention, LayerNorm, Linear, Mlp, _as_hip_norm, _cfg, bias_or_zero, block_params,
                              build_2d_sincos_posemb, pair, trunc_normal_)
 
@@ -344,11 +347,139 @@ class ConvNeXtAdapter(nn.Module):
 
 
 class DPTOutputAdapter(nn.Module):
-    """Name only (output_adapters.py:576-...): the DPT head is not built in this engine."""
+    """DPT head (output_adapters.py:576-759) with the regression head type, the one every shipped depth and Taskonomy recipe uses:
+    four hooked encoder layers are reassembled into maps at 4x, 2x, 1x and 1/2x the token grid (act_1..4_postprocess), projected to
+    feature_dim (scratch.layer_rn), fused coarse to fine by four RefineNet blocks (scratch.refinenet4..1) and turned into a
+    (B, num_classes, H, W) f32 image by the head.  Same constructor signature, attribute names, parameter names, registration order
+    and seeded initialisation as the reference: at the reference's default geometry the state_dict has its 82 keys in its order, and
+    a reference DPT checkpoint loads with load_state_dict(strict=True).  nn.ConvTranspose2d / nn.Conv2d are parameter holders.
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError('DPTOutputAdapter (the DPT semantic-segmentation head) is not built in multimae_amd; '
-                                  'use ConvNeXtAdapter (--output_adapter convnext)')
+    forward() takes the list of all encoder layers' tokens (MultiViT.forward(return_all_layers=True)) and runs ten autograd nodes:
+    four functions.DPTReassembleFn, the four fusion blocks, functions.DPTHeadFn.  The prediction is a plain contiguous NCHW tensor
+    (no LazyPrediction, no low-resolution handle: the head's output is at image resolution already).
+
+    Not built (NotImplementedError naming the argument): use_bn=True, head_type='semseg', num_classes > 16 (the regression tail
+    kernel keeps one accumulator per output channel in registers; 16 is also the limit of the regression losses).  The token grid
+    must be even in both directions (the reference fails on an odd one as well).  bf16 mode needs every channel count to be a
+    multiple of 8 (ValueError); engine.set_precision('fp32') runs every product on the exact-f32 path and takes any.  The head runs
+    uncaptured only: it is untested under graph capture, as the fusion blocks."""
+
+    MAX_CLASSES = 16             # == ops.DPT_TAIL_MAX_K
+
+    def __init__(self, num_classes: int = 3, stride_level: int = 1, patch_size: Union[int, Tuple[int, int]] = 16,
+                 main_tasks: Iterable[str] = ('rgb',), hooks: List[int] = [2, 5, 8, 11], layer_dims: List[int] = [96, 192, 384, 768],
+                 feature_dim: int = 256, use_bn: bool = False, dim_tokens_enc: Optional[int] = None, head_type: str = 'regression',
+                 **kwargs):
+        super().__init__()
+        if head_type not in ('regression', 'semseg'):
+            raise ValueError(f'DPTOutputAdapter: head_type must be "regression" or "semseg", got {head_type!r}')
+        if head_type == 'semseg':
+            raise NotImplementedError("DPTOutputAdapter: head_type = 'semseg' is not built in multimae_amd (its Dropout and optional "
+                                      "BatchNorm are further work); the regression head is")
+        if use_bn:
+            raise NotImplementedError('DPTOutputAdapter: use_bn = True is not built in multimae_amd')
+        if num_classes > self.MAX_CLASSES:
+            raise NotImplementedError(f'DPTOutputAdapter: num_classes = {num_classes} > {self.MAX_CLASSES} is not built in multimae_amd '
+                                      '(the regression tail kernel keeps one accumulator per output channel in registers)')
+        if num_classes < 1:
+            raise ValueError(f'DPTOutputAdapter: num_classes = {num_classes} must be at least 1')
+        self.num_channels = num_classes
+        self.stride_level = stride_level
+        self.patch_size = pair(patch_size)
+        self.main_tasks = main_tasks
+        self.hooks = hooks
+        self.layer_dims = layer_dims
+        self.feature_dim = feature_dim
+        self.dim_tokens_enc = dim_tokens_enc * len(self.main_tasks) if dim_tokens_enc is not None else None
+        self.head_type = head_type
+
+        self.P_H = max(1, self.patch_size[0] // stride_level)
+        self.P_W = max(1, self.patch_size[1] // stride_level)
+
+        self.scratch = make_scratch(layer_dims, feature_dim, groups=1, expand=False)
+        self.scratch.refinenet1 = make_fusion_block(feature_dim, use_bn)
+        self.scratch.refinenet2 = make_fusion_block(feature_dim, use_bn)
+        self.scratch.refinenet3 = make_fusion_block(feature_dim, use_bn)
+        self.scratch.refinenet4 = make_fusion_block(feature_dim, use_bn)
+
+        # the "DPTDepthModel" head (output_adapters.py:627-633); run as one node by forward(), the modules hold the parameters
+        self.head = nn.Sequential(
+            Conv3x3(feature_dim, feature_dim // 2, stride=1, bias=True),
+            Interpolate(scale_factor=2, mode='bilinear', align_corners=True),
+            Conv3x3(feature_dim // 2, 32, stride=1, bias=True),
+            nn.ReLU(True),
+            nn.Conv2d(32, self.num_channels, kernel_size=1, stride=1, padding=0))
+
+        if self.dim_tokens_enc is not None:
+            self.init(dim_tokens_enc=dim_tokens_enc)
+
+    def init(self, dim_tokens_enc: int = 768):
+        """the parts that depend on the encoder width (output_adapters.py:650-715): act_1..4_postprocess, also listed in
+        act_postprocess (both sets of keys appear in a state_dict, as in the reference)"""
+        self.dim_tokens_enc = dim_tokens_enc * len(self.main_tasks)
+        D, L = self.dim_tokens_enc, self.layer_dims
+        self.act_1_postprocess = nn.Sequential(
+            nn.Conv2d(in_channels=D, out_channels=L[0], kernel_size=1, stride=1, padding=0),
+            nn.ConvTranspose2d(in_channels=L[0], out_channels=L[0], kernel_size=4, stride=4, padding=0, bias=True, dilation=1, groups=1))
+        self.act_2_postprocess = nn.Sequential(
+            nn.Conv2d(in_channels=D, out_channels=L[1], kernel_size=1, stride=1, padding=0),
+            nn.ConvTranspose2d(in_channels=L[1], out_channels=L[1], kernel_size=2, stride=2, padding=0, bias=True, dilation=1, groups=1))
+        self.act_3_postprocess = nn.Sequential(
+            nn.Conv2d(in_channels=D, out_channels=L[2], kernel_size=1, stride=1, padding=0))
+        self.act_4_postprocess = nn.Sequential(
+            nn.Conv2d(in_channels=D, out_channels=L[3], kernel_size=1, stride=1, padding=0),
+            nn.Conv2d(in_channels=L[3], out_channels=L[3], kernel_size=3, stride=2, padding=1))
+        self.act_postprocess = nn.ModuleList([self.act_1_postprocess, self.act_2_postprocess, self.act_3_postprocess,
+                                              self.act_4_postprocess])
+
+    def _layer_params(self, i: int):
+        ps = []
+        for m in self.act_postprocess[i]:
+            ps += [m.weight, m.bias]
+        return ps + [self.scratch.layer_rn[i].weight]
+
+    def forward(self, encoder_tokens: List[torch.Tensor], input_info: Dict):
+        """list of (B, N_total, D) encoder-layer tokens -> f32 (B, num_classes, H, W) prediction (output_adapters.py:728-759)"""
+        if self.dim_tokens_enc is None or not hasattr(self, 'act_postprocess'):
+            raise ValueError('DPTOutputAdapter: init(dim_tokens_enc) must be called before forward()')
+        if isinstance(encoder_tokens, torch.Tensor) or len(encoder_tokens) < max(self.hooks) + 1:
+            n = 1 if isinstance(encoder_tokens, torch.Tensor) else len(encoder_tokens)
+            raise ValueError(f'DPTOutputAdapter: encoder_tokens must list the tokens of every encoder layer up to hook {max(self.hooks)} '
+                             f'(MultiViT.forward(return_all_layers=True)); got {n}')
+        H, W = input_info['image_size']
+        NH = H // (self.stride_level * self.P_H)
+        NW = W // (self.stride_level * self.P_W)
+        starts, counts = [], []
+        for task in self.main_tasks:
+            info = input_info['tasks'][task]
+            starts.append(int(info['start_idx']))
+            counts.append(int(info['end_idx']) - int(info['start_idx']))
+        if len(set(counts)) != 1 or counts[0] != NH * NW:
+            raise ValueError(f'DPTOutputAdapter: the main_tasks {tuple(self.main_tasks)} have {counts} tokens; each needs the '
+                             f'{NH} x {NW} grid of the {H} x {W} image')
+        layers = [encoder_tokens[hook] for hook in self.hooks]
+        D = layers[0].shape[-1]
+        if any(l.dim() != 3 or l.shape != layers[0].shape for l in layers) or D * len(starts) != self.dim_tokens_enc:
+            raise ValueError(f'DPTOutputAdapter: encoder width {D} x {len(starts)} tasks != the dim_tokens_enc of init() '
+                             f'({self.dim_tokens_enc}), or the hooked layers differ in shape')
+        if NH % 2 or NW % 2:
+            raise ValueError(f'DPTOutputAdapter: the token grid N_H x N_W = {NH} x {NW} must be even in both directions (act_4_postprocess '
+                             'halves it and refinenet4 doubles it again; the reference fails on an odd grid too)')
+        cfg0 = _conv_cfg(self)
+        chans = (self.dim_tokens_enc, *self.layer_dims, self.feature_dim, self.feature_dim // 2)
+        if cfg0.act != torch.float32 and any(c % 8 for c in chans):
+            raise ValueError(f'DPTOutputAdapter: the bf16 gathers and GEMMs need channel counts that are multiples of 8 (dim_tokens_enc x '
+                             f'tasks, layer_dims, feature_dim, feature_dim // 2 = {chans}); use engine.set_precision("fp32") for this geometry')
+        maps = []
+        for i, tok in enumerate(layers):
+            cfg = _conv_cfg(self, layer=i, starts=starts, N=NH * NW, NH=NH, NW=NW)
+            maps.append(DPTReassembleFn.apply(cfg, tok, *self._layer_params(i)))
+        path_4 = self.scratch.refinenet4(maps[3])
+        path_3 = self.scratch.refinenet3(path_4, maps[2])
+        path_2 = self.scratch.refinenet2(path_3, maps[1])
+        path_1 = self.scratch.refinenet1(path_2, maps[0])
+        h = self.head
+        return DPTHeadFn.apply(cfg0, path_1, h[0].weight, h[0].bias, h[2].weight, h[2].bias, h[4].weight, h[4].bias)
 
 
 class SegmenterMaskTransformerAdapter(nn.Module):
