@@ -1132,6 +1132,29 @@ int mmae_depth_metrics(const float* x, int64_t ldx, const float* target, const v
                        int mode, float* partial, float* out, float* acc, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * The same losses and metrics on a prediction that is the image itself -- the DPT head's output --, csrc/regloss.hip: pred f32
+ * [B][K][H][W] contiguous, no interpolation and no map; target, mask, kind, diff, partial and out as in the block above, any K >= 1.
+ * Element-wise streaming kernels with 64-bit element indices: 16-byte accesses (four elements a thread, their mask bytes as one
+ * word) when H W % 4 == 0, pred / target / diff are 16-byte aligned and the mask 4-byte aligned, one element a thread otherwise;
+ * the finish kernels of the block above.  No float atomics; results are bit-equal from run to run; no host synchronisation.
+ * MMAE_EINVAL before any launch for a NULL pointer other than mask and acc, a non-positive B, K, H, W or n, a kind outside 0..2, or
+ * a mask whose mask_channels is neither 1 nor K.
+ *   reg_img_fwd:        diff[e] = mask ? pred[e] - target[e] : 0 -- one subtraction; a NaN or inf under a false mask reaches nothing.
+ *                       out f32 [4] = loss, count of valid elements (as f32), max |diff|, c = max(0.2f max|diff|, 1e-5f), exactly
+ *                       reg_loss_fwd's contract (count == 0: loss 0); berHu sums over the stored diff once c is known.
+ *                       partial f32 [4 MMAE_REG_PARTIALS] (scratch).
+ *   reg_img_bwd:        dpred f32 [n] = up[0] / out[1] * g(diff[e]), n = B K H W, g and the scale as in reg_loss_bwd (d|d| / dd at 0 is
+ *                       0, berHu's c is a constant): an invalid element gets exactly 0, count == 0 all zeros.
+ *   depth_metrics_img:  depth_metrics for K = 1 with z = pred[e]: out f32 [7] (NaN when nothing is valid), partial f32
+ *                       [8 MMAE_REG_PARTIALS] (scratch), acc f32 [8] or NULL: acc[0..6] += out, acc[7] += 1.
+ * ------------------------------------------------------------------------- */
+int mmae_reg_img_fwd(const float* pred, const float* target, const void* mask, int mask_channels, int kind, int B, int K, int H, int W,
+                     float* diff, float* partial, float* out, void* stream);
+int mmae_reg_img_bwd(const float* diff, const float* out, const float* up, int kind, int64_t n, float* dpred, void* stream);
+int mmae_depth_metrics_img(const float* pred, const float* target, const void* mask, float mean, float std, int B, int H, int W,
+                           float* partial, float* out, float* acc, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The classification fine-tuning recipe (run_finetuning_cls.py: --mixup / --cutmix / --smoothing / --model_ema), csrc/clsrecipe.hip.
  * No float atomics; results are bit-equal from run to run.  mixup_pairs, mix_target and ema_update are bit-identical to the
  * reference's eager f32 expressions (every product and sum rounds on its own: no FMA contraction).

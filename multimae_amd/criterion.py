@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import engine, ops
-from .functions import MaskedCEFn, MaskedCEPatFn, MaskedPixelLossFn, MaskedPixelLossPatFn, RegLossFn, SegCEFn, SoftCEFn
+from .functions import MaskedCEFn, MaskedCEPatFn, MaskedPixelLossFn, MaskedPixelLossPatFn, RegImageLossFn, RegLossFn, SegCEFn, SoftCEFn
 from .lazy import materialize as _materialize
 
 
@@ -181,11 +181,35 @@ def _refuse_under_capture(pred, what: str) -> None:
                            'untested; run this step uncaptured')
 
 
+def _image_fused_ok(preds, target, mask_valid, channels=None) -> bool:
+    """The conditions of the fused path on a prediction that is the image itself: the DPT head's own output, still carrying its mark
+    (functions.ImageMark: same shape, not modified in place since) with engine.patch_domain_loss() on, f32 and contiguous (with
+    `channels` channels when given); an f32 target of its shape on its device; no mask or a torch.bool mask [B, 1 or K, H, W] on that
+    device; no graph capture running (the head runs uncaptured only: anything met inside a capture takes the eager path)."""
+    mark = getattr(preds, '_mmae_img', None) if torch.is_tensor(preds) else None
+    if mark is None or not engine.patch_domain_loss() or not mark.matches(preds):
+        return False
+    if preds.dim() != 4 or preds.dtype != torch.float32 or not preds.is_contiguous() or (channels is not None and preds.shape[1] != channels):
+        return False
+    if engine.capturing() is not None or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+        return False
+    dev = preds.device
+    if not torch.is_tensor(target) or target.dtype != torch.float32 or tuple(target.shape) != tuple(preds.shape) or target.device != dev:
+        return False
+    if mask_valid is None:
+        return True
+    B, K, H, W = preds.shape
+    return (torch.is_tensor(mask_valid) and mask_valid.dtype == torch.bool and mask_valid.device == dev and mask_valid.dim() == 4
+            and mask_valid.shape[1] in (1, K) and (mask_valid.shape[0],) + tuple(mask_valid.shape[2:]) == (B, H, W))
+
+
 def _reg_loss(preds, target, mask_valid, kind: str) -> torch.Tensor:
     _refuse_under_capture(preds, f'masked_{kind}_loss')
     h = _seg_handle(preds)
     if _reg_fused_ok(h, preds, target, mask_valid):
         return RegLossFn.apply(h.token, h, target, mask_valid, kind)
+    if _image_fused_ok(preds, target, mask_valid):
+        return RegImageLossFn.apply(preds, target, mask_valid, kind)
     return _reg_loss_eager(preds, target, mask_valid, kind)
 
 
@@ -193,9 +217,14 @@ def masked_l1_loss(preds, target, mask_valid=None):
     """``masked_l1_loss`` of run_finetuning_depth.py:59-66: mean |preds - target| over the valid elements.  On an unmodified f32
     prediction of the ConvNeXt head (``preds[task].float()`` is the same object) with an f32 target of its shape and a torch.bool mask
     of 1 or K channels, the loss and its gradient come from the head's low-resolution map (functions.RegLossFn) and the image is
-    neither written nor read; a mask without a valid element then gives 0 with a zero gradient (the reference: NaN).  Anything else --
-    a modified prediction, more than 16 channels, a CPU tensor -- is evaluated on the image.  Not inside a graph capture: a head
-    prediction met while a graph.StepGraph or torch.cuda.graph capture runs raises RuntimeError (_refuse_under_capture)."""
+    neither written nor read.  On the DPT head's own f32 prediction (it carries functions.ImageMark; ``preds[task].float()`` is the
+    same object) under the same conditions on target and mask, the loss and its gradient come from the fused kernels on the image
+    (functions.RegImageLossFn, any number of channels).  On both fused paths a mask without a valid element gives 0 with a zero
+    gradient (the reference: NaN).  Anything else -- ``y * 1``, ``y.clone()`` of a DPT prediction, a prediction modified in place,
+    more than 16 channels of the ConvNeXt head, another dtype, a non-bool mask, engine.set_patch_domain_loss(False), a CPU tensor --
+    is evaluated on the image by _reg_loss_eager.  Not inside a graph capture: a ConvNeXt-head prediction met while a
+    graph.StepGraph or torch.cuda.graph capture runs raises RuntimeError (_refuse_under_capture); a DPT prediction takes the eager
+    path there."""
     return _reg_loss(preds, target, mask_valid, 'l1')
 
 

@@ -1427,6 +1427,45 @@ class RegLossFn(torch.autograd.Function):
             diff, out, up, ctx.kind, *h.geom(), torch.empty_like(h.logits), h.ld), 4)
 
 
+class ImageMark:
+    """What DPTOutputAdapter.forward leaves on the tensor it returns (``out._mmae_img``): the shape and the version counter of the
+    head's own contiguous f32 NCHW prediction.  The regression losses and the depth metrics take their fused kernels on the image
+    (RegImageLossFn, ops.depth_metrics_img) only for a tensor that still carries a matching mark; a derived tensor (``y * 1``,
+    ``y.clone()``) has none, and a prediction modified in place no longer matches."""
+    __slots__ = ('shape', 'version')
+
+    def __init__(self, shape, version: int):
+        self.shape, self.version = tuple(shape), int(version)
+
+    def matches(self, img: Tensor) -> bool:
+        return tuple(img.shape) == self.shape and img._version == self.version
+
+
+class RegImageLossFn(torch.autograd.Function):
+    """masked_l1_loss / masked_mse_loss / masked_berhu_loss (kind 'l1' / 'mse' / 'berhu') on a prediction that is the image itself, the
+    DPT head's f32 contiguous (B, K, H, W) output (csrc/regloss.hip, mmae_reg_img_*): an ordinary node whose input is the image, its
+    gradient d_preds f32 contiguous NCHW.  mask: torch.bool [B, 1 or K, H, W] or None.  A batch without a valid element gives an f32
+    zero with a zero gradient (the reference: NaN).  No host synchronisation: berHu's threshold stays on the device."""
+
+    @staticmethod
+    def forward(ctx, preds: Tensor, target: Tensor, mask: Optional[Tensor], kind: str):
+        ops._require_gpu(preds, 'loss input')
+        ctx.kind = kind
+        target = target.contiguous()
+        diff, out = ops.reg_img_fwd(preds, target, None if mask is None else mask.contiguous(), kind)
+        ctx.saved = (target, diff, out, target._version)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        target, diff, out, version = ctx.saved
+        ctx.saved = None
+        if target._version != version:
+            raise RuntimeError('a tensor saved for the regression-loss backward was modified in place')
+        up = g.contiguous().float().reshape(1)
+        return ops.reg_img_bwd(diff, out, up, ctx.kind), None, None, None
+
+
 class SoftCEFn(torch.autograd.Function):
     """SoftTargetCrossEntropy (dense f32 target [B, K]) or LabelSmoothingCrossEntropy (int64 labels [B] + smoothing) of the classification
     head's logits [B, K], f32 or bf16 (csrc/clsrecipe.hip): forward and backward are one launch each, the gradient comes back in the

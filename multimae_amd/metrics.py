@@ -7,8 +7,9 @@ them with one all-reduce and evaluates the ratios of ``eval_metrics`` (:216-222)
 to K counted into class K - 1) is not reproduced: predictions and labels outside [0, K) are dropped.
 
 Depth evaluation (``masked_nyu_metrics``, run_finetuning_depth.py:86-117, about thirty small launches and -- through
-``MetricLogger.update`` -- one ``.item()`` per metric and step): ``depth_metrics`` computes the seven values in one pass over the head's
-low-resolution map, ``DepthMetric`` keeps MetricLogger's running means on the device and reads them back once.
+``MetricLogger.update`` -- one ``.item()`` per metric and step): ``depth_metrics`` computes the seven values in one pass over the
+ConvNeXt head's low-resolution map or over the DPT head's image, ``DepthMetric`` keeps MetricLogger's running means on the device and
+reads them back once.
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .criterion import _refuse_under_capture, _seg_handle
+from .criterion import _image_fused_ok, _refuse_under_capture, _seg_handle
 
 
 def seg_argmax(pred: torch.Tensor, num_classes: int) -> torch.Tensor:
@@ -108,6 +109,9 @@ def _depth_values(pred, target, mask_valid, mean, std, acc=None) -> torch.Tensor
     if _depth_fused_ok(h, pred, target, mask_valid):
         mask = None if mask_valid is None else mask_valid.contiguous()
         return ops.depth_metrics(h.logits, h.ld, target.contiguous(), mask, mean, std, h.B, h.h, h.w, h.H, h.W, h.mode, acc=acc)
+    if _image_fused_ok(pred, target, mask_valid, channels=1):
+        mask = None if mask_valid is None else mask_valid.contiguous()       # the DPT head's own one-channel prediction
+        return ops.depth_metrics_img(pred, target.contiguous(), mask, mean, std, acc=acc)
     out = _depth_metrics_eager(pred, target, mask_valid, mean, std).float()
     if acc is not None:
         acc[:7] += out
@@ -120,7 +124,9 @@ def depth_metrics(pred: torch.Tensor, target: torch.Tensor, mask_valid=None, mea
     delta_1, delta_2, delta_3 of pred std + mean against target std + mean over the valid pixels, as a dict of 0-dim device tensors;
     nothing is read back.  On an unmodified one-channel prediction of the ConvNeXt head with an f32 target and a torch.bool mask of
     its shape the values come from one pass over the head's low-resolution map (csrc/regloss.hip) and the image is not written.
-    A head prediction inside a graph capture raises RuntimeError (criterion._refuse_under_capture)."""
+    On the DPT head's own one-channel f32 prediction (functions.ImageMark) under the same conditions they come from one pass over
+    the image (mmae_depth_metrics_img); every other prediction -- more channels, ``y * 1``, modified in place -- is evaluated by
+    _depth_metrics_eager.  A ConvNeXt-head prediction inside a graph capture raises RuntimeError (criterion._refuse_under_capture)."""
     out = _depth_values(pred, target, mask_valid, mean, std)
     return {k: out[i] for i, k in enumerate(DEPTH_METRIC_KEYS)}
 

@@ -1797,6 +1797,78 @@ def depth_metrics(x: Tensor, ldx: int, target: Tensor, mask: Optional[Tensor], m
     return out
 
 
+# ------------------------------------------------- ... and on a prediction that is the image itself (the DPT head's output) ----------
+def _img_args(pred: Tensor, target: Tensor, mask: Optional[Tensor], what: str):
+    """(B, K, H, W, mask pointer, mask channels) of a contiguous f32 [B, K, H, W] prediction, a target like it and a contiguous
+    torch.bool mask [B, 1 or K, H, W] or None; ValueError otherwise"""
+    if pred.dim() != 4 or pred.dtype != torch.float32 or not pred.is_contiguous() or pred.numel() == 0:
+        raise ValueError(f'{what}: the prediction is a non-empty contiguous float32 [B, K, H, W] tensor')
+    if tuple(target.shape) != tuple(pred.shape) or target.dtype != torch.float32 or not target.is_contiguous() \
+            or target.device != pred.device:
+        raise ValueError(f'{what}: the target is a contiguous float32 tensor of the prediction\'s shape {tuple(pred.shape)} on its device')
+    B, K, H, W = pred.shape
+    if mask is None:
+        return B, K, H, W, None, 1
+    if mask.dtype != torch.bool or not mask.is_contiguous() or mask.dim() != 4 or mask.shape[1] not in (1, K) \
+            or (mask.shape[0], mask.shape[2], mask.shape[3]) != (B, H, W) or mask.device != pred.device:
+        raise ValueError(f'{what}: the mask is a contiguous torch.bool [B, 1 or K, H, W] tensor on the prediction\'s device')
+    return B, K, H, W, mask.data_ptr(), int(mask.shape[1])
+
+
+def _img_buf(t: Optional[Tensor], shape, like: Tensor, what: str) -> Tensor:
+    if t is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f'{what}: a contiguous float32 tensor of shape {tuple(shape)} on the prediction\'s device')
+    return t
+
+
+def reg_img_fwd(pred: Tensor, target: Tensor, mask: Optional[Tensor], kind: str, diff: Optional[Tensor] = None,
+                partial: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """masked L1 / MSE / berHu of a prediction that is the image: pred, target f32 [B, K, H, W] contiguous, mask torch.bool
+    [B, 1 or K, H, W] or None -> (diff f32 [B, K, H, W] = pred - target, 0 where masked, out f32 [4] = (loss, valid count, max |diff|,
+    berHu's c)); nothing is read back to the host."""
+    if kind not in REG_KINDS:
+        raise ValueError(f'reg_img_fwd: kind must be one of {tuple(REG_KINDS)}, got {kind!r}')
+    B, K, H, W, mp, cm = _img_args(pred, target, mask, 'reg_img_fwd')
+    diff = _img_buf(diff, (B, K, H, W), pred, 'reg_img_fwd: diff')
+    partial = _img_buf(partial, (4 * REG_PARTIALS,), pred, 'reg_img_fwd: partial')
+    out = _img_buf(out, (4,), pred, 'reg_img_fwd: out')
+    check(_lib.load().mmae_reg_img_fwd(pred.data_ptr(), target.data_ptr(), mp, cm, REG_KINDS[kind], B, K, H, W, diff.data_ptr(),
+                                       partial.data_ptr(), out.data_ptr(), _stream()), 'reg_img_fwd')
+    return diff, out
+
+
+def reg_img_bwd(diff: Tensor, out: Tensor, up: Tensor, kind: str, dpred: Optional[Tensor] = None) -> Tensor:
+    """its gradient: dpred f32 (diff's shape) = up / count * g(diff), exactly 0 on an invalid element; up f32 [1] on the device"""
+    if kind not in REG_KINDS:
+        raise ValueError(f'reg_img_bwd: kind must be one of {tuple(REG_KINDS)}, got {kind!r}')
+    if diff.dtype != torch.float32 or not diff.is_contiguous() or diff.numel() == 0:
+        raise ValueError('reg_img_bwd: diff is the non-empty contiguous float32 tensor reg_img_fwd returned')
+    if out.dtype != torch.float32 or out.numel() != 4 or up.dtype != torch.float32 or up.numel() != 1:
+        raise ValueError('reg_img_bwd: out is reg_img_fwd\'s float32 [4], up one float32 on the device')
+    dpred = _img_buf(dpred, diff.shape, diff, 'reg_img_bwd: dpred')
+    check(_lib.load().mmae_reg_img_bwd(diff.data_ptr(), out.data_ptr(), up.data_ptr(), REG_KINDS[kind], diff.numel(), dpred.data_ptr(),
+                                       _stream()), 'reg_img_bwd')
+    return dpred
+
+
+def depth_metrics_img(pred: Tensor, target: Tensor, mask: Optional[Tensor], mean: float, std: float, acc: Optional[Tensor] = None,
+                      out: Optional[Tensor] = None, partial: Optional[Tensor] = None) -> Tensor:
+    """the seven NYU depth metrics of a one-channel prediction that is the image (f32 [B, 1, H, W] contiguous): out f32 [7] = rmse,
+    rel, srel, log10, delta_1..3; acc f32 [8] (optional): the seven values are added to acc[:7] and acc[7] += 1 on the device"""
+    B, K, H, W, mp, _ = _img_args(pred, target, mask, 'depth_metrics_img')
+    if K != 1:
+        raise ValueError(f'depth_metrics_img: the depth metrics take one channel, got {K}')
+    partial = _img_buf(partial, (8 * REG_PARTIALS,), pred, 'depth_metrics_img: partial')
+    out = _img_buf(out, (7,), pred, 'depth_metrics_img: out')
+    if acc is not None:
+        _img_buf(acc, (8,), pred, 'depth_metrics_img: acc')
+    check(_lib.load().mmae_depth_metrics_img(pred.data_ptr(), target.data_ptr(), mp, float(mean), float(std), B, H, W, partial.data_ptr(),
+                                             out.data_ptr(), _p(acc), _stream()), 'depth_metrics_img')
+    return out
+
+
 # ------------------------------------------------- classification fine-tuning recipe (csrc/clsrecipe.hip) --------------------------
 MIX_ROW_WORDS = 8            # MMAE_MIX_ROW_WORDS: w_self, w_other, t_self, t_other (f32), yl, yh, xl, xh (i32) per sample
 MIX_BLEND, MIX_KEEP = -1, -2  # MMAE_MIX_BLEND / MMAE_MIX_KEEP in the yl word: blend without a box / sample not written

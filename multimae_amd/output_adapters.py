@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import engine
-from .functions import ConvNeXtHeadFn, DPTHeadFn, DPTReassembleFn, SpatialAdapterFn, TokenMeanFn
+from .functions import ConvNeXtHeadFn, DPTHeadFn, DPTReassembleFn, ImageMark, SpatialAdapterFn, TokenMeanFn
 from .output_adapter_utils import Conv3x3, Interpolate, _conv_cfg, make_fusion_block, make_scratch
 from .multimae_utils import (Block, CrossAttention, LayerNorm, Linear, Mlp, _as_hip_norm, _cfg, bias_or_zero, block_params,
                              build_2d_sincos_posemb, pair, trunc_normal_)
@@ -356,10 +356,12 @@ class DPTOutputAdapter(nn.Module):
 
     forward() takes the list of all encoder layers' tokens (MultiViT.forward(return_all_layers=True)) and runs ten autograd nodes:
     four functions.DPTReassembleFn, the four fusion blocks, functions.DPTHeadFn.  The prediction is a plain contiguous NCHW tensor
-    (no LazyPrediction, no low-resolution handle: the head's output is at image resolution already).
+    (no LazyPrediction, no low-resolution handle: the head's output is at image resolution already).  With
+    engine.patch_domain_loss() on and no capture running it carries ``_mmae_img`` (functions.ImageMark), by which the regression
+    losses and the depth metrics recognise it and run their fused kernels on the image.
 
     Not built (NotImplementedError naming the argument): use_bn=True, head_type='semseg', num_classes > 16 (the regression tail
-    kernel keeps one accumulator per output channel in registers; 16 is also the limit of the regression losses).  The token grid
+    kernel keeps one accumulator per output channel in registers; 16 is also the limit of the regression losses on the ConvNeXt head's map).  The token grid
     must be even in both directions (the reference fails on an odd one as well).  bf16 mode needs every channel count to be a
     multiple of 8 (ValueError); engine.set_precision('fp32') runs every product on the exact-f32 path and takes any.  The head runs
     uncaptured only: it is untested under graph capture, as the fusion blocks."""
@@ -479,7 +481,12 @@ class DPTOutputAdapter(nn.Module):
         path_2 = self.scratch.refinenet2(path_3, maps[1])
         path_1 = self.scratch.refinenet1(path_2, maps[0])
         h = self.head
-        return DPTHeadFn.apply(cfg0, path_1, h[0].weight, h[0].bias, h[2].weight, h[2].bias, h[4].weight, h[4].bias)
+        out = DPTHeadFn.apply(cfg0, path_1, h[0].weight, h[0].bias, h[2].weight, h[2].bias, h[4].weight, h[4].bias)
+        if engine.patch_domain_loss() and engine.capturing() is None and not (out.is_cuda and torch.cuda.is_current_stream_capturing()):
+            # the regression losses and the depth metrics run their fused kernels on exactly this tensor while it is unmodified
+            # (criterion._image_fused_ok); still a plain torch.Tensor, and no low-resolution handle
+            out._mmae_img = ImageMark(out.shape, out._version)
+        return out
 
 
 class SegmenterMaskTransformerAdapter(nn.Module):
