@@ -236,6 +236,15 @@ def depth_metric(device=None):
     return DepthMetric(device)
 
 
+def cls_metric(topk=(1, 5), device=None):
+    """Replaces ``criterion`` + ``accuracy`` + the three ``.item()`` read-backs of ``evaluate()`` (run_finetuning_cls.py:582-613): call
+    ``metric.update(output, target)`` per batch, then ``metric.sync()`` and ``metric.compute()`` -- the only read-back -- for
+    MetricLogger's ``global_avg`` of ``loss``, ``acc1`` and ``acc5``.  The training loop's ``class_acc`` line (:541) is
+    ``multimae_amd.cls_accuracy(output, targets)[0] / 100`` without its read-back."""
+    from multimae_amd.metrics import ClsMetric
+    return ClsMetric(topk, device)
+
+
 def prepare_dense_inputs(input_dict: dict, tasks_dict: dict, standardize_depth: bool) -> dict:
     """Replaces the two blocks between the ``input_dict`` comprehension and the forward pass of run_finetuning_depth.py (:671-695
     in ``train_one_epoch``, :808-832 in ``evaluate``) and of run_finetuning_taskonomy.py (:645-668, :766-789), without a sort, a

@@ -1191,6 +1191,32 @@ int mmae_soft_ce_bwd(const void* x, int x_dtype, int64_t ldx, const float* targe
                      const float* lse, const float* tsum, const float* up, void* dx, void* stream);
 int mmae_ema_update(float* ema, const float* p, void* shadow, int64_t n, float decay, float one_minus_decay, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Classification evaluation, csrc/clseval.hip: what evaluate() of run_finetuning_cls.py:580-613 computes per batch with
+ * nn.CrossEntropyLoss (:600), utils/metrics.py accuracy (:31-38: topk's sort, a transpose, an eq, two reductions; :602) and three
+ * .item() read-backs (:605-607), and the class_acc line of the training loop (:541), in two launches with no sort, no host
+ * synchronisation and no float atomics; every sum has a fixed order, results are bit-equal from run to run.
+ *   x [B][ldx] (first K columns; columns K .. ldx - 1 are never read), x_dtype MMAE_F32 or MMAE_BF16 (read as f32); target int64 [B].
+ *   Row kernel, one workgroup per row b, t = target[b], valid = 0 <= t < K, z_t = x[b][t]:
+ *     lse  f32 [B]    log-sum-exp of the row (soft_ce_fwd's recurrence and trees: its error bound holds)
+ *     nll  f32 [B]    valid ? lse - z_t : 0
+ *     rank i32 [B]    valid ? #{k: z_k > z_t} + #{k < t: z_k == z_t} : K
+ *   THE TIE RULE is part of the interface: row b is correct at k iff rank[b] < min(k, K); among equal logits the lower index ranks
+ *   first (mmae_seg_argmax's rule; torch.topk leaves that order unspecified).  A target outside [0, K) -- ignore_index -100
+ *   included -- is left out of the loss and is incorrect at every k; B stays the accuracies' denominator, as in accuracy().
+ *   Finish kernel, one workgroup, n_k in [1, MMAE_CLS_TOPK_MAX] thresholds k0 .. k3 (each >= 1; the ones past n_k are ignored):
+ *     out f32 [1 + n_k]  out[0] = loss = n_valid > 0 ? (float)(sum nll / n_valid) : 0, summed in double in a fixed tree (torch gives NaN
+ *                        for a batch without a valid target); out[1 + j] = fl(fl((float)c_j * 100.f) / (float)B), c_j the exact count
+ *                        of rows correct at k_j -- the f32 operations of utils/metrics.py:38
+ *     acc f64 [3 + n_k] or NULL: MetricLogger's total / count pairs (utils/logger.py, SmoothedValue.update), added by the same launch:
+ *                        acc[0] += (double)loss, acc[1] += 1, acc[2] += B, acc[3 + j] += (double)out[1 + j] * B
+ * MMAE_EINVAL before any launch, with nothing written, for a NULL pointer other than acc, B <= 0, K <= 0, ldx < K, n_k outside
+ * [1, MMAE_CLS_TOPK_MAX] or a k_j < 1 (j < n_k); MMAE_ESUPPORT for any other dtype code.
+ * ------------------------------------------------------------------------- */
+#define MMAE_CLS_TOPK_MAX 4
+int mmae_cls_eval(const void* x, int x_dtype, int64_t ldx, const int64_t* target, int B, int K, int n_k, int k0, int k1, int k2, int k3,
+                  float* lse, float* nll, int32_t* rank, float* out, double* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

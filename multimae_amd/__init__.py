@@ -11,7 +11,7 @@ from .criterion import (LabelSmoothingCrossEntropy, MaskedCrossEntropyLoss, Mask
                         SegCrossEntropyLoss, SoftTargetCrossEntropy, masked_berhu_loss, masked_l1_loss, masked_mse_loss)
 from .ema import ModelEma  # noqa: F401
 from .mixup import Mixup  # noqa: F401
-from .metrics import DepthMetric, SegMetric, depth_metrics, seg_argmax  # noqa: F401
+from .metrics import ClsMetric, DepthMetric, SegMetric, cls_accuracy, depth_metrics, seg_argmax  # noqa: F401
 from .input_adapters import PatchedInputAdapter, SemSegInputAdapter  # noqa: F401
 from .multimae import (MultiMAE, MultiViT, multivit_base, multivit_large,  # noqa: F401
                        pretrain_multimae_base, pretrain_multimae_large)

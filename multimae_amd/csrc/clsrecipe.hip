@@ -89,15 +89,7 @@ __global__ void __launch_bounds__(256) mix_target_kernel(const long long* __rest
 }
 
 // ---- soft-target cross-entropy ------------------------------------------------------------------------------------------------------
-// fixed-order sums / maxima over the 256 threads of a workgroup: xor-shuffle tree inside a wave, the four waves in wave order
-__device__ __forceinline__ void put_wave(float v, float* sh) {
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-}
-__device__ __forceinline__ float block_sum(float v, float* sh) { put_wave(wave_sum(v), sh); return join4_sum(sh); }
-__device__ __forceinline__ float block_max(float v, float* sh) { put_wave(wave_max(v), sh); return join4_max(sh); }
-
+// (block_sum / block_max, the fixed-order sums and maxima over the workgroup: common.h)
 // the target of element k of a row: the dense row, or smoothing / K + (1 - smoothing) [k == label]
 struct Tgt {
     const float* dense;

@@ -265,6 +265,15 @@ __device__ __forceinline__ float wave_max(float v) {
 // the four waves' values of a 256-thread workgroup (sh[wave]) joined in wave order
 __device__ __forceinline__ float join4_sum(const float* sh) { return ((sh[0] + sh[1]) + sh[2]) + sh[3]; }
 __device__ __forceinline__ float join4_max(const float* sh) { return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])); }
+// fixed-order sums / maxima over the 256 threads of a workgroup (sh: 4 floats of LDS): xor-shuffle tree inside a wave, the four waves
+// in wave order; every thread must call and gets the result (csrc/clsrecipe.hip soft_ce_fwd, csrc/clseval.hip: one error bound)
+__device__ __forceinline__ void put_wave(float v, float* sh) {
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+}
+__device__ __forceinline__ float block_sum(float v, float* sh) { put_wave(wave_sum(v), sh); return join4_sum(sh); }
+__device__ __forceinline__ float block_max(float v, float* sh) { put_wave(wave_max(v), sh); return join4_max(sh); }
 // a fixed tree over the 256 threads' values (each usually a strided pre-sum) through the LDS array s[256]: 128 .. 1; every thread
 // must call and gets the result; s is not to be written again before a barrier
 template <class T, class Op>

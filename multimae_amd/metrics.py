@@ -10,6 +10,11 @@ Depth evaluation (``masked_nyu_metrics``, run_finetuning_depth.py:86-117, about 
 ``MetricLogger.update`` -- one ``.item()`` per metric and step): ``depth_metrics`` computes the seven values in one pass over the
 ConvNeXt head's low-resolution map or over the DPT head's image, ``DepthMetric`` keeps MetricLogger's running means on the device and
 reads them back once.
+
+Classification evaluation (``evaluate()`` of run_finetuning_cls.py:580-613: ``nn.CrossEntropyLoss``, ``accuracy``'s topk sort and three
+``.item()`` read-backs per batch): ``cls_accuracy`` and ``ClsMetric`` take the top-k correctness of a row from the rank of its target's
+logit, counted in the pass that computes the log-sum-exp (csrc/clseval.hip, two launches), keep MetricLogger's totals in one f64 device
+buffer and read it back once.
 """
 from __future__ import annotations
 
@@ -176,6 +181,124 @@ class DepthMetric:
         v = tot.double().cpu()
         vals = torch.cat([v[:7], v[8:]]) / v[7]
         return {k: float(x) for k, x in zip(self.names, vals)}
+
+
+# ------------------------------------------------------------------------------------------
+# Classification evaluation (run_finetuning_cls.py:580-613, utils/metrics.py:31-38)
+# ------------------------------------------------------------------------------------------
+def _topk_arg(topk):
+    ks = tuple(int(k) for k in topk)
+    if not ks or min(ks) < 1:
+        raise ValueError(f'topk must hold at least one threshold, each >= 1, got {tuple(topk)}')
+    return ks
+
+
+def _cls_args(output, target):
+    if not (torch.is_tensor(output) and output.dim() == 2 and torch.is_tensor(target) and target.dim() == 1
+            and target.shape[0] == output.shape[0]):
+        raise ValueError('classification metrics take (B, K) logits and B class indices')
+    if target.dtype.is_floating_point or target.dtype == torch.bool:
+        raise ValueError(f'classification metrics take integer class indices, got {target.dtype}')
+
+
+def _cls_fused_ok(output, target, ks) -> bool:
+    B, K = output.shape
+    if not (output.dtype in (torch.float32, torch.bfloat16) and ops._device_ok(output) and B > 0 and K > 0):
+        return False
+    if not ((K == 1 or output.stride(1) == 1) and (B == 1 or output.stride(0) >= K)):
+        return False
+    return target.dtype == torch.int64 and target.device == output.device and len(ks) <= ops.CLS_TOPK_MAX
+
+
+def _cls_rank_eager(z, target):
+    """(valid [B], z_t [B], rank int64 [B]) by the kernel's rule: rank = #{k: z_k > z_t} + #{k < t: z_k == z_t} through comparisons
+    (no topk: its order among equal logits is unspecified), K for a target outside [0, K)"""
+    K = z.shape[1]
+    t = target.long()
+    valid = (t >= 0) & (t < K)
+    tc = t.clamp(0, K - 1)
+    zt = z.gather(1, tc[:, None])
+    idx = torch.arange(K, device=z.device)
+    rank = (z > zt).sum(1) + ((z == zt) & (idx[None, :] < tc[:, None])).sum(1)
+    return valid, zt.squeeze(1), torch.where(valid, rank, torch.full_like(rank, K))
+
+
+def _cls_eval_eager(output, target, ks) -> torch.Tensor:
+    """mmae_cls_eval's out (f32 [1 + len(ks)] = loss, percentages) restated in torch without a sort or a read-back: the loss is the
+    mean of lse - z_t over the valid targets (0 without one), summed in double; the percentages are accuracy()'s f32 operations"""
+    B, K = output.shape
+    z = output if output.dtype in (torch.float32, torch.float64) else output.float()
+    valid, zt, rank = _cls_rank_eager(z, target)
+    nll = torch.where(valid, torch.logsumexp(z, 1) - zt, torch.zeros_like(zt))
+    nv = valid.sum()
+    loss = torch.where(nv > 0, nll.double().sum() / nv.clamp_min(1), torch.zeros((), dtype=torch.float64, device=z.device)).float()
+    accs = [(rank < min(k, K)).float().sum(0) * 100. / B for k in ks]
+    return torch.stack([loss] + accs)
+
+
+@torch.no_grad()
+def _cls_values(output, target, ks, acc=None) -> torch.Tensor:
+    _cls_args(output, target)
+    output = output.detach()
+    B, K = output.shape
+    if _cls_fused_ok(output, target, ks) and (acc is None or acc.device == output.device):
+        ldx = output.stride(0) if B > 1 else K
+        return ops.cls_eval(output, ldx, B, K, target.contiguous(), ks, acc=acc)[3]
+    out = _cls_eval_eager(output, target, ks)
+    if acc is not None:
+        acc[0] += out[0].double()
+        acc[1] += 1
+        acc[2] += B
+        acc[3:] += out[1:].double() * B
+    return out
+
+
+def cls_accuracy(output: torch.Tensor, target: torch.Tensor, topk=(1,)):
+    """``utils.metrics.accuracy(output, target, topk)``: the percentage of rows whose target is among the k largest logits, as a list of
+    0-dim f32 device tensors; nothing is read back.  A row is correct at k iff fewer than min(k, K) logits rank before its target's,
+    equal logits ranking by index (the lower first) -- where the reference's topk leaves ties unspecified.  A target outside [0, K)
+    is incorrect at every k and B stays the denominator.  2-D f32 / bf16 GPU logits with unit inner stride, an int64 target and at
+    most four thresholds run in two launches (csrc/clseval.hip, beside the cross-entropy); anything else takes _cls_eval_eager."""
+    ks = _topk_arg(topk)
+    out = _cls_values(output, target, ks)
+    return [out[1 + j] for j in range(len(ks))]
+
+
+class ClsMetric:
+    """What ``MetricLogger`` keeps in ``evaluate()`` of run_finetuning_cls.py (:600-607), on the device: the plain cross-entropy of
+    every batch (``update(loss=loss.item())``: total += loss, count += 1) and the top-k accuracies weighted by the batch size
+    (``meters['acc1'].update(acc1.item(), n=batch_size)``) in one f64 buffer [3 + len(topk)] = loss total, batches, samples, acc totals.
+
+    update(output, target)   adds the batch; two launches on the fused path, no read-back on either path
+    sync()                   one all_reduce of the buffer when torch.distributed is initialised
+    compute()                {'loss': ..., 'acc1': ..., 'acc5': ...} (keys f'acc{k}') as Python floats, MetricLogger's global_avg --
+                             the only read-back
+    A target outside [0, K) (ignore_index -100 included) is left out of the loss and counts as incorrect; a batch without a valid
+    target has loss 0 (torch: NaN) and still counts as a batch."""
+
+    def __init__(self, topk=(1, 5), device=None):
+        self.topk = _topk_arg(topk)
+        self.acc = None if device is None else torch.zeros((3 + len(self.topk),), device=device, dtype=torch.float64)
+
+    def reset(self) -> None:
+        if self.acc is not None:
+            self.acc.zero_()
+
+    @torch.no_grad()
+    def update(self, output: torch.Tensor, target: torch.Tensor) -> None:
+        if self.acc is None:
+            self.acc = torch.zeros((3 + len(self.topk),), device=target.device, dtype=torch.float64)
+        _cls_values(output, target, self.topk, acc=self.acc)
+
+    def sync(self) -> None:
+        if self.acc is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.all_reduce(self.acc)
+
+    def compute(self):
+        v = self.acc.cpu()
+        res = {'loss': float(v[0] / v[1])}
+        res.update({f'acc{k}': float(v[3 + j] / v[2]) for j, k in enumerate(self.topk)})
+        return res
 
 
 def ratios(hist: np.ndarray):

@@ -1918,3 +1918,38 @@ def ema_update(ema: Tensor, p: Tensor, decay: float, shadow: Optional[Tensor] = 
     check(_lib.load().mmae_ema_update(ema.data_ptr(), p.data_ptr(), _p(shadow), ema.numel(), float(decay), float(1. - decay), _stream()),
           'ema_update')
     return ema
+
+
+# ------------------------------------------------- classification evaluation (csrc/clseval.hip) ------------------------------------
+CLS_TOPK_MAX = 4             # MMAE_CLS_TOPK_MAX: thresholds one mmae_cls_eval call takes
+
+
+def cls_eval(x: Tensor, ldx: int, B: int, K: int, target: Tensor, topk: Sequence[int], acc: Optional[Tensor] = None,
+             lse: Optional[Tensor] = None, nll: Optional[Tensor] = None, rank: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """Plain cross-entropy and top-k accuracies of logits x [B, ldx] f32 / bf16 (first K columns) against target int64 [B] in two
+    launches: (lse f32 [B], nll f32 [B], rank int32 [B], out f32 [1 + len(topk)] = mean loss over the valid targets, percentages).
+    Row b is correct at k iff rank[b] < min(k, K) (ties: the lower index first).  acc f64 [3 + len(topk)] (optional) receives
+    MetricLogger's totals on the device: acc[0] += loss, acc[1] += 1, acc[2] += B, acc[3 + j] += out[1 + j] * B.  Nothing is read back."""
+    ks = [int(k) for k in topk]
+    n_k = len(ks)
+    if not 1 <= n_k <= CLS_TOPK_MAX or min(ks) < 1:
+        raise ValueError(f'cls_eval: 1 to {CLS_TOPK_MAX} thresholds >= 1, got {tuple(topk)}')
+    if target.dtype != torch.int64 or tuple(target.shape) != (B,) or not target.is_contiguous():
+        raise ValueError(f'cls_eval: target must be a contiguous int64 tensor of {B} class indices')
+    if acc is not None and (acc.dtype != torch.float64 or tuple(acc.shape) != (3 + n_k,) or not acc.is_contiguous()):
+        raise ValueError(f'cls_eval: acc must be a contiguous float64 tensor of {3 + n_k} elements')
+    ws = None
+    if lse is None or nll is None or rank is None or out is None:
+        ws = torch.empty((3 * B + 1 + n_k,), device=x.device, dtype=torch.float32)   # one allocation: lse, nll, rank (as int32), out
+    lse = ws[:B] if lse is None else lse
+    nll = ws[B:2 * B] if nll is None else nll
+    rank = ws[2 * B:3 * B].view(torch.int32) if rank is None else rank
+    out = ws[3 * B:] if out is None else out
+    for t, dt, n, name in ((lse, torch.float32, B, 'lse'), (nll, torch.float32, B, 'nll'), (rank, torch.int32, B, 'rank'),
+                           (out, torch.float32, 1 + n_k, 'out')):
+        if t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f'cls_eval: {name} must be a contiguous {dt} tensor of {n} elements')
+    k4 = ks + [0] * (CLS_TOPK_MAX - n_k)
+    check(_lib.load().mmae_cls_eval(x.data_ptr(), dcode(x.dtype), int(ldx), target.data_ptr(), int(B), int(K), n_k, k4[0], k4[1], k4[2], k4[3],
+                                    lse.data_ptr(), nll.data_ptr(), rank.data_ptr(), out.data_ptr(), _p(acc), _stream()), 'cls_eval')
+    return lse, nll, rank, out
