@@ -12,7 +12,11 @@ hooks (13.4 ms), the 345 ``torch.norm`` calls of ``get_grad_norm_`` (9.9 ms), DD
       run_pretraining_multimae.py:380-382                        readiness-ordered arenas), direct gradients, dist.GradAllReducer
                                                                  + dist.attach: buckets all-reduced over RCCL while backward runs
   create_optimizer(args, {'model': .., 'balancer': ..})          create_optimizer(args, model): optim.FusedAdamW -- the ONE group
-      :389-390, utils/optim_factory.py:138-174                   the dict branch builds (weight decay on every trainable tensor)
+      :389-390, utils/optim_factory.py:138-174                   the dict branch builds (weight decay on every trainable tensor);
+                                                                 with ``--task_balancer uncertainty`` its two groups, the balancer's
+                                                                 (lr_scale = balancer_lr_scale) outside the gradient norm and the clip
+  UncertaintyWeightingStrategy(tasks=..) / NoWeightingStrategy   task_balancer(args): the engine's strategies -- the weighting and its
+      :316-319, utils/task_balancing.py                          backward as one launch each, ``log_vars`` inside the parameter arena
   NativeScaler()  (GradScaler + unscale_ + get_grad_norm_)       LossScaler(): same call signature and return value (the gradient
       :391, utils/native_scaler.py:14-62                         2-norm); backward, reducer.finish(), ONE fused library call for
                                                                  norm + clip / skip + non-finite guard + AdamW.  bf16 needs no
@@ -26,7 +30,7 @@ hooks (13.4 ms), the 345 ``torch.norm`` calls of ``get_grad_norm_`` (9.9 ms), DD
   loss_scaler(..., update_grad=False)  (--update_freq > 1)       LossScaler: the backward of an accumulation micro-step runs inside
       run_finetuning_cls.py:528-531                              reducer.hold() -- gradients are exchanged once per update
 
-The patch that wires them in is ``dropin/run_pretraining_multimae.patch`` (three call sites).  Everything else in the script --
+The patch that wires them in is ``dropin/run_pretraining_multimae.patch`` (four call sites).  Everything else in the script --
 argument parsing, cosine tables, the per-iteration ``param_group['lr']`` assignment (:474-480), ``train_one_epoch`` itself,
 logging, ``utils.save_model`` -- stays the reference's.  ``tests/test_dropin_loop_gpu.py`` runs the loop body with these services at
 the bench geometry against the native loop.
@@ -43,11 +47,29 @@ from multimae_amd import dist as mdist
 from multimae_amd.optim import FusedAdamW
 
 
-def wrap_model(model: torch.nn.Module, args=None, bucket_mb: float = 64.0):
-    """Replaces the DistributedDataParallel wrap (run_pretraining_multimae.py:380-382).  Returns ``(model, reducer)``: the model is
+def task_balancer(args) -> torch.nn.Module:
+    """Replaces the balancer construction (run_pretraining_multimae.py:316-319): ``multimae_amd.UncertaintyWeightingStrategy`` over
+    ``args.out_domains`` for ``--task_balancer uncertainty``, ``NoWeightingStrategy`` for ``none``."""
+    kind = getattr(args, 'task_balancer', 'none')
+    if kind == 'uncertainty':
+        return M.UncertaintyWeightingStrategy(tasks=args.out_domains)
+    if kind == 'none':
+        return M.NoWeightingStrategy()
+    raise ValueError(f'amd_loop.task_balancer: --task_balancer {kind!r} is not one of none, uncertainty')
+
+
+def _trainable_balancer(balancer) -> bool:
+    return balancer is not None and any(p.requires_grad for p in balancer.parameters())
+
+
+def wrap_model(model: torch.nn.Module, args=None, bucket_mb: float = 64.0, balancer=None):
+    """Replaces the DistributedDataParallel wraps (run_pretraining_multimae.py:380-387).  Returns ``(model, reducer)``: the model is
     NOT wrapped (``model_without_ddp is model``; checkpoints keep the reference's keys), the reducer is None outside
-    torch.distributed.  Rank 0's parameters are broadcast as DDP's constructor does (the script seeds every rank differently, :300-302)."""
-    arena = model.build_arena()
+    torch.distributed.  Rank 0's parameters are broadcast as DDP's constructor does (the script seeds every rank differently, :300-302).
+    ``balancer``: the loss balancer (already on the model's device); its trainable ``log_vars`` joins the END of the arena's trainable
+    prefix, so the broadcast, the reducer's last bucket (its gradient is averaged over the ranks as under the script's second DDP
+    wrap, :385-387) and the fused step cover it.  Neither ``state_dict()`` changes."""
+    arena = model.build_arena(extra={'balancer': balancer}) if _trainable_balancer(balancer) else model.build_arena()
     M.engine.set_direct_grads(True)              # backward writes straight into the gradient arena: no AccumulateGrad per parameter
     on_gpu = arena.param.is_cuda                 # (a CPU dry run of the host logic has no streams)
     M.engine.set_adapter_streams(on_gpu)
@@ -61,27 +83,45 @@ def wrap_model(model: torch.nn.Module, args=None, bucket_mb: float = 64.0):
     return model, reducer
 
 
-def create_optimizer(args, model: torch.nn.Module, reducer=None) -> FusedAdamW:
+def create_optimizer(args, model: torch.nn.Module, reducer=None, balancer=None) -> FusedAdamW:
     """Replaces utils.optim_factory.create_optimizer(args, {'model': model, 'balancer': balancer}) for the pre-training recipe
-    (``--opt adamw``, ``--task_balancer none``: the balancer group is empty, utils/optim_factory.py:138-155)."""
+    (``--opt adamw``).  ``--task_balancer none``: the balancer group is empty (utils/optim_factory.py:138-155) -- the ONE group of
+    every trainable tensor, whatever ``balancer`` is.  ``--task_balancer uncertainty``: the two groups of :139-150 -- the model's
+    tensors with ``lr_scale`` 1, the balancer's with ``args.balancer_lr_scale``, both with ``args.weight_decay`` (``log_vars``
+    decays too) -- the balancer's outside the gradient norm, the clip and the skip decision, as the loop's
+    ``parameters=model.parameters()`` has it (run_pretraining_multimae.py:536-537); ``balancer`` must be the one
+    ``wrap_model(..., balancer=...)`` put into the arena, otherwise ValueError."""
     _check_adamw_args(args)
-    return _fused(args, model, reducer, args.weight_decay)
+    if getattr(args, 'task_balancer', 'none') == 'none':
+        return _fused(args, model, reducer, args.weight_decay)
+    if not _trainable_balancer(balancer):
+        raise ValueError('amd_loop.create_optimizer: --task_balancer uncertainty needs the balancer whose log_vars the optimiser '
+                         'steps: create_optimizer(args, model, reducer, balancer=loss_balancer)')
+    arena = M.engine.arena_of(model)
+    bal = [p for p in balancer.parameters() if p.requires_grad]
+    if arena is None or not all(any(arena._params.get(n) is p for n in arena.extra_names) for p in bal):
+        raise ValueError('amd_loop.create_optimizer: the balancer\'s parameters are not in the model\'s arena; call '
+                         'wrap_model(model, args, balancer=loss_balancer) first')
+    groups = [dict(params=[p for _, p in model.named_parameters() if p.requires_grad], lr_scale=1.),
+              dict(params=bal, lr_scale=args.balancer_lr_scale)]
+    return _fused(args, model, reducer, args.weight_decay, groups=groups, norm_exempt=bal)
 
 
 def _check_adamw_args(args) -> None:
     if getattr(args, 'opt', 'adamw').lower().split('_')[-1] != 'adamw':
         raise ValueError('amd_loop.create_optimizer: the fused step is AdamW (--opt adamw); use the reference factory for other optimisers')
-    if getattr(args, 'task_balancer', 'none') != 'none':
-        raise ValueError('amd_loop.create_optimizer: --task_balancer uncertainty has trainable balancer weights outside the arena; '
-                         'use the reference factory (the drop-in seam still works, at the reference loop\'s speed)')
+    if getattr(args, 'task_balancer', 'none') not in ('none', 'uncertainty'):
+        raise ValueError(f'amd_loop.create_optimizer: --task_balancer {args.task_balancer!r} is not one of none, uncertainty')
 
 
-def _fused(args, model, reducer, weight_decay, groups=None) -> FusedAdamW:
+def _fused(args, model, reducer, weight_decay, groups=None, norm_exempt=None) -> FusedAdamW:
     kw = dict(lr=args.lr, weight_decay=weight_decay)
     if getattr(args, 'opt_eps', None) is not None:
         kw['eps'] = args.opt_eps
     if getattr(args, 'opt_betas', None) is not None:
         kw['betas'] = tuple(args.opt_betas)
+    if norm_exempt is not None:
+        kw['norm_exempt'] = norm_exempt
     opt = FusedAdamW(model, groups=groups, **kw) if groups is not None else FusedAdamW(model, **kw)
     reducer = reducer if reducer is not None else getattr(model, '_amd_reducer', None)
     if reducer is not None:

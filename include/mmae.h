@@ -902,6 +902,39 @@ typedef struct mmae_opt_groups_desc {
 int mmae_opt_step_groups(const mmae_opt_groups_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * mmae_opt_step_groups with a NORM-EXEMPT TAIL: the optimiser's parameters that the loop does not hand to the loss scaler.
+ * run_pretraining_multimae.py:536-537 passes parameters=model.parameters(), so get_grad_norm_ / clip_grad_norm_
+ * (utils/native_scaler.py:20-40) see the model's gradients only, while the optimiser of utils/optim_factory.py:138-150 also
+ * steps the task balancer's log_vars (the second param group): its gradient enters neither the norm nor the clip.
+ *   g[0, n_norm)   the sum of squares -- hence the norm, the clip coefficient, the skip_grad and the non-finite decisions and
+ *                  istate[5] -- covers this prefix only; its elements are scaled by state[2] as in mmae_opt_step_groups
+ *   g[n_norm, n)   scaled by the UNCLIPPED gradient scale grad_prescale / (grad_scale_dev ? *grad_scale_dev : 1), which this
+ *                  entry point records in state[7]; a non-finite value here alone skips nothing and counts nowhere
+ * The skip flag (a skipped step skips both parts), the step counter, the bias corrections, the per-group lr / weight decay
+ * (hyper by value or hyper_dev), the shadow and every other state / istate slot are mmae_opt_step_groups'.
+ * n_norm: a positive multiple of 64, <= n.  n_norm == n gives mmae_opt_step_groups' results bit for bit.  ABI v7.
+ * ------------------------------------------------------------------------- */
+int mmae_opt_step_groups_tail(const mmae_opt_groups_desc* d, int64_t n_norm, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Uncertainty task balancer: UncertaintyWeightingStrategy.forward (utils/task_balancing.py:31-44) and its backward, one
+ * launch each (one wave, plain stores, no host read-back: usable inside a captured step).  T <= MMAE_BALANCE_MAX_TASKS.
+ *   fwd  L_i = *loss_ptrs[i] (loss_ptrs: HOST array of T device pointers, copied into the launch's arguments during the
+ *        call -- the task losses are T separate device scalars) or losses[i] (packed device f32 [T]); exactly one is given.
+ *        weighted[i] = (exp(-log_vars[i]) * L_i + log_vars[i]) * (L_i != 0)     (task_balancing.py:33-39; NaN != 0)
+ *        saved f32 [2 T] = { exp(-log_vars[i]) }, { L_i }: the backward evaluates no expf and reads no loss again
+ *   bwd  u_i = *upstream_ptrs[i] (host array of T device pointers, a null entry = no gradient, 0) or upstream[i] (packed)
+ *        d_losses[i]   = u_i * exp(-s_i) * (L_i != 0)
+ *        d_log_vars[i] = (accumulate ? d_log_vars[i] : 0) + u_i * (1 - exp(-s_i) * L_i) * (L_i != 0)
+ *        (d_log_vars may be log_vars' view of the gradient arena: accumulate = 0 stores over known zeros.)
+ * ------------------------------------------------------------------------- */
+#define MMAE_BALANCE_MAX_TASKS 16
+int mmae_task_balance_fwd(const float* const* loss_ptrs, const float* losses, const float* log_vars, float* weighted,
+                          float* saved, int T, void* stream);
+int mmae_task_balance_bwd(const float* const* upstream_ptrs, const float* upstream, const float* saved, float* d_losses,
+                          float* d_log_vars, int accumulate, int T, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Truncated depth standardisation, the step right before the model in the training loop
  * (run_pretraining_multimae.py:487-492): per sample, mean / unbiased variance of the values of rank [lo, hi) among
  * the n = c*h*w values (the reference: torch.sort, slice [int(0.1 n), int(0.9 n)), mean, var), then

@@ -18,5 +18,6 @@ from .multimae import (MultiMAE, MultiViT, multivit_base, multivit_large,  # noq
 from .output_adapters import LinearOutputAdapter, SpatialOutputAdapter  # noqa: F401
 from .registry import create_model, register_model  # noqa: F401
 from .staging import BatchStager, StagedLoader  # noqa: F401
+from .task_balancing import NoWeightingStrategy, UncertaintyWeightingStrategy  # noqa: F401
 
 __version__ = '0.1.0'

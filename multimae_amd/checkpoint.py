@@ -110,7 +110,8 @@ def _group_entry(g, ids) -> dict:
 def optimizer_state_to_torch(opt) -> dict:
     """FusedAdamW moments -> ``torch.optim.AdamW.state_dict()`` layout (one param group, state per trainable tensor).  A grouped
     FusedAdamW (``group_names`` set) gives the layout of ``torch.optim.AdamW(groups)``: state indices numbered group by group,
-    each group's tensors in its own order, and every group's hyper-parameters."""
+    each group's tensors in its own order, and every group's hyper-parameters.  The pre-training optimiser with the uncertainty
+    balancer is such a one: group 0 the model's tensors, group 1 the balancer's ``log_vars`` (utils/optim_factory.py:139-150)."""
     if getattr(opt, 'group_names', None) is not None:
         return _grouped_state_to_torch(opt)
     g = opt.param_groups[0]
@@ -169,8 +170,9 @@ def _grouped_state_from_torch(opt, sd: dict) -> None:
 
 def optimizer_state_from_torch(opt, sd: dict) -> None:
     """Load a ``torch.optim.AdamW`` state dict (e.g. from a reference checkpoint) into FusedAdamW's flat moments.  Extra param
-    groups (the reference's loss-balancer group) are ignored; the schedule values are taken from group 0.  A grouped FusedAdamW
-    takes a state of exactly its own group layout (same number of groups and of tensors in each), every group's values."""
+    groups (the reference's loss-balancer group) are ignored when the optimiser has no balancer group; the schedule values are
+    taken from group 0.  A grouped FusedAdamW takes a state of exactly its own group layout (same number of groups and of tensors
+    in each), every group's values -- with ``--task_balancer uncertainty`` the model's group and the balancer's, both loaded."""
     if getattr(opt, 'group_names', None) is not None:
         _grouped_state_from_torch(opt, sd)
         return
@@ -236,14 +238,17 @@ def latest_checkpoint(output_dir: str) -> Optional[str]:
     return os.path.join(output_dir, f'checkpoint-{best}.pth') if best >= 0 else None
 
 
-def load_checkpoint(path: str, model, optimizer=None, resize_pos_emb: bool = True) -> int:
+def load_checkpoint(path: str, model, optimizer=None, resize_pos_emb: bool = True, loss_balancer=None) -> int:
     """Resume (utils/checkpoint.py:115-131): model weights, and -- if present -- optimiser state and epoch.  Accepts
-    checkpoints written by the reference or by save_checkpoint.  Returns the epoch to start from."""
+    checkpoints written by the reference or by save_checkpoint.  ``loss_balancer``: restored (strictly) from the checkpoint's
+    ``'loss_balancer'`` entry (utils/checkpoint.py:89-90) when it has one.  Returns the epoch to start from."""
     ckpt = torch.load(path, map_location='cpu', weights_only=False)
     sd = ckpt['model'] if 'model' in ckpt else ckpt
     if resize_pos_emb:
         interpolate_pos_embed_multimae(model, sd)
     model.load_state_dict(sd)
+    if loss_balancer is not None and 'loss_balancer' in ckpt:
+        loss_balancer.load_state_dict(ckpt['loss_balancer'], strict=True)
     start = 0
     if optimizer is not None and 'optimizer' in ckpt and 'epoch' in ckpt:
         if hasattr(optimizer, 'arena'):

@@ -537,7 +537,7 @@ __global__ void __launch_bounds__(256) sumsq_stage2(const float* __restrict__ ws
 // counter and bias corrections.  One thread.
 __global__ void opt_finalize_kernel(float* __restrict__ state, int* __restrict__ istate, float lr, float wd, const float* __restrict__ lrwd,
                                     float b1, float b2, float clip, float skip_at, float prescale, const float* __restrict__ loss,
-                                    const float* __restrict__ found_inf, const float* __restrict__ grad_scale) {
+                                    const float* __restrict__ found_inf, const float* __restrict__ grad_scale, int tail) {
     if (grad_scale) prescale /= grad_scale[0];             // GradScaler's loss scale, still on the gradients (mmae.h)
     const float norm = sqrtf(state[0]) * prescale;
     const bool loss_bad = loss && !isfinite(loss[0]);
@@ -560,6 +560,7 @@ __global__ void opt_finalize_kernel(float* __restrict__ state, int* __restrict__
     const int te = t > 0 ? t : 1;
     state[5] = (float)(1.0 - pow((double)b1, (double)te));
     state[6] = (float)sqrt(1.0 - pow((double)b2, (double)te));
+    if (tail) state[7] = prescale;                         // mmae_opt_step_groups_tail: the unclipped scale of the norm-exempt tail
 }
 
 template <typename ST>
@@ -614,15 +615,19 @@ struct GroupHyperDev {
 // there (its lr / weight decay are uniform, these per chunk, which lets the compiler pick other products to fuse): the
 // vector path and the scalar tail of adamw_kernel contract differently, and so do these, so one group gives adamw_kernel's
 // results bit for bit.  bc[0..1] = 1 - beta1^t, sqrt(1 - beta2^t) from opt_finalize_kernel.
-template <typename ST, typename HY>
+// TAIL (mmae_opt_step_groups_tail): elements [n_norm, n) take *tail_scale, the unclipped gradient scale, instead of *grad_scale;
+// n_norm is a multiple of 64, so a 16 B run lies on one side of it.  The expressions are the same: n_norm == n changes no bit.
+template <typename ST, typename HY, bool TAIL>
 __global__ void __launch_bounds__(256) adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, long long n, const uint16_t* __restrict__ gmap,
                                                            int n_groups, const HY hy, float b1, float b2, float eps,
                                                            const float* __restrict__ bc, const float* __restrict__ grad_scale,
-                                                           const int* __restrict__ skip, ST* __restrict__ shadow) {
+                                                           const int* __restrict__ skip, ST* __restrict__ shadow, long long n_norm,
+                                                           const float* __restrict__ tail_scale) {
     if (skip && *skip) return;
     const float bc1 = bc[0], bc2_sqrt = bc[1];
-    const float gs = grad_scale ? *grad_scale : 1.f;
+    const float gs_norm = grad_scale ? *grad_scale : 1.f;
+    const float gs_tail = TAIL ? *tail_scale : gs_norm;
     for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long long)gridDim.x * 1024) {
         float lr, wd;
         if (i + 4 <= n) {
@@ -630,6 +635,7 @@ __global__ void __launch_bounds__(256) adamw_groups_kernel(float* __restrict__ p
             const int k = gmap[i >> 6];
             f32x4 pv = ld4(p + i), mv = ld4(m + i), vv = ld4(v + i);
             const f32x4 gv = ld4(g + i);
+            const float gs = (TAIL && i >= n_norm) ? gs_tail : gs_norm;
             hy.get(k < n_groups ? k : n_groups - 1, lr, wd);
             const float decay = fmaf(-lr, wd, 1.f), step = lr / bc1;
 #pragma unroll
@@ -646,7 +652,7 @@ __global__ void __launch_bounds__(256) adamw_groups_kernel(float* __restrict__ p
             for (long long j = i; j < n; ++j) {
                 const int k = gmap[j >> 6];
                 hy.get(k < n_groups ? k : n_groups - 1, lr, wd);
-                const float gj = g[j] * gs;
+                const float gj = g[j] * ((TAIL && j >= n_norm) ? gs_tail : gs_norm);
                 const float mj = fmaf(1.f - b1, gj, b1 * m[j]), vj = fmaf(gj, (1.f - b2) * gj, b2 * v[j]);
                 const float pj = fmaf(fmaf(-lr, wd, 1.f), p[j], -((lr / bc1) * (mj / (sqrtf(vj) / bc2_sqrt + eps))));
                 p[j] = pj; m[j] = mj; v[j] = vj;
@@ -656,18 +662,18 @@ __global__ void __launch_bounds__(256) adamw_groups_kernel(float* __restrict__ p
     }
 }
 
-template <typename HY>
-int launch_adamw_groups(const mmae_opt_groups_desc* d, const HY& hy, hipStream_t st) {
+template <bool TAIL, typename HY>
+int launch_adamw_groups(const mmae_opt_groups_desc* d, const HY& hy, hipStream_t st, long long n_norm = 0) {
     long long nb = cdiv64(d->n, 1024);
     if (nb > 8192) nb = 8192;
     const float* bc = d->state + 5;
     const float* gsc = d->state + 2;
     if (d->shadow && d->shadow_dtype == MMAE_BF16)
-        hipLaunchKernelGGL((adamw_groups_kernel<uint16_t, HY>), dim3((unsigned)nb), dim3(256), 0, st, d->p, d->g, d->m, d->v, (long long)d->n,
-                           d->group_map, (int)d->n_groups, hy, d->beta1, d->beta2, d->eps, bc, gsc, (const int*)d->istate, (uint16_t*)d->shadow);
+        hipLaunchKernelGGL((adamw_groups_kernel<uint16_t, HY, TAIL>), dim3((unsigned)nb), dim3(256), 0, st, d->p, d->g, d->m, d->v, (long long)d->n,
+                           d->group_map, (int)d->n_groups, hy, d->beta1, d->beta2, d->eps, bc, gsc, (const int*)d->istate, (uint16_t*)d->shadow, n_norm, (const float*)(d->state + 7));
     else
-        hipLaunchKernelGGL((adamw_groups_kernel<float, HY>), dim3((unsigned)nb), dim3(256), 0, st, d->p, d->g, d->m, d->v, (long long)d->n,
-                           d->group_map, (int)d->n_groups, hy, d->beta1, d->beta2, d->eps, bc, gsc, (const int*)d->istate, (float*)d->shadow);
+        hipLaunchKernelGGL((adamw_groups_kernel<float, HY, TAIL>), dim3((unsigned)nb), dim3(256), 0, st, d->p, d->g, d->m, d->v, (long long)d->n,
+                           d->group_map, (int)d->n_groups, hy, d->beta1, d->beta2, d->eps, bc, gsc, (const int*)d->istate, (float*)d->shadow, n_norm, (const float*)(d->state + 7));
     return mmae_check_launch("adamw_groups");
 }
 
@@ -869,7 +875,7 @@ int mmae_opt_step(const mmae_opt_desc* d, void* stream) {
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(opt_finalize_kernel, dim3(1), dim3(1), 0, st, d->state, d->istate, d->lr, d->weight_decay, d->lrwd_dev, d->beta1, d->beta2,
-                       d->clip_grad, d->skip_grad, d->grad_prescale, d->loss_dev, d->found_inf_dev, d->grad_scale_dev);
+                       d->clip_grad, d->skip_grad, d->grad_prescale, d->loss_dev, d->found_inf_dev, d->grad_scale_dev, 0);
     if ((rc = mmae_check_launch("opt_finalize"))) return rc;
     return mmae_adamw_dev(d->p, d->g, d->m, d->v, d->n, d->state + 3, d->beta1, d->beta2, d->eps, d->state + 2, d->istate, d->shadow,
                           d->shadow_dtype, stream);
@@ -889,12 +895,35 @@ int mmae_opt_step_groups(const mmae_opt_groups_desc* d, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const float lr0 = d->hyper_dev ? 0.f : d->hyper[0], wd0 = d->hyper_dev ? 0.f : d->hyper[1];
     hipLaunchKernelGGL(opt_finalize_kernel, dim3(1), dim3(1), 0, st, d->state, d->istate, lr0, wd0, d->hyper_dev, d->beta1, d->beta2,
-                       d->clip_grad, d->skip_grad, d->grad_prescale, d->loss_dev, d->found_inf_dev, d->grad_scale_dev);
+                       d->clip_grad, d->skip_grad, d->grad_prescale, d->loss_dev, d->found_inf_dev, d->grad_scale_dev, 0);
     if ((rc = mmae_check_launch("opt_finalize"))) return rc;
-    if (d->hyper_dev) return launch_adamw_groups(d, GroupHyperDev{d->hyper_dev}, st);
+    if (d->hyper_dev) return launch_adamw_groups<false>(d, GroupHyperDev{d->hyper_dev}, st);
     GroupHyperVal hv;
     for (int k = 0; k < 2 * MMAE_OPT_MAX_GROUPS; ++k) hv.v[k] = k < 2 * d->n_groups ? d->hyper[k] : 0.f;
-    return launch_adamw_groups(d, hv, st);
+    return launch_adamw_groups<false>(d, hv, st);
+}
+
+int mmae_opt_step_groups_tail(const mmae_opt_groups_desc* d, int64_t n_norm, void* stream) {
+    MMAE_REQUIRE(d && d->p && d->g && d->m && d->v && d->n > 0 && d->state && d->istate && d->ws && d->group_map,
+                 "opt_step_groups_tail: bad argument");
+    MMAE_REQUIRE(n_norm > 0 && n_norm % 64 == 0 && n_norm <= d->n, "opt_step_groups_tail: n_norm must be a positive multiple of 64, <= n");
+    MMAE_REQUIRE(d->grad_prescale > 0.f, "opt_step_groups_tail: grad_prescale must be positive (1 for a single process)");
+    MMAE_REQUIRE(d->hyper_dev ? (d->n_groups >= 1 && d->n_groups <= 65536) : (d->hyper && d->n_groups >= 1 && d->n_groups <= MMAE_OPT_MAX_GROUPS),
+                 "opt_step_groups_tail: n_groups out of range, or neither hyper nor hyper_dev given");
+    MMAE_REQUIRE(((uintptr_t)d->p % 16 == 0) && ((uintptr_t)d->g % 16 == 0) && ((uintptr_t)d->m % 16 == 0) && ((uintptr_t)d->v % 16 == 0)
+                 && ((uintptr_t)d->group_map % 2 == 0), "opt_step_groups_tail: unaligned");
+    MMAE_REQUIRE(shadow_ok(d->shadow, d->shadow_dtype), "opt_step_groups_tail" MMAE_SHADOW_MSG);
+    int rc = mmae_sumsq(d->g, n_norm, d->state, d->ws, stream);        // the norm sees the prefix only
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const float lr0 = d->hyper_dev ? 0.f : d->hyper[0], wd0 = d->hyper_dev ? 0.f : d->hyper[1];
+    hipLaunchKernelGGL(opt_finalize_kernel, dim3(1), dim3(1), 0, st, d->state, d->istate, lr0, wd0, d->hyper_dev, d->beta1, d->beta2,
+                       d->clip_grad, d->skip_grad, d->grad_prescale, d->loss_dev, d->found_inf_dev, d->grad_scale_dev, 1);
+    if ((rc = mmae_check_launch("opt_finalize"))) return rc;
+    if (d->hyper_dev) return launch_adamw_groups<true>(d, GroupHyperDev{d->hyper_dev}, st, (long long)n_norm);
+    GroupHyperVal hv;
+    for (int k = 0; k < 2 * MMAE_OPT_MAX_GROUPS; ++k) hv.v[k] = k < 2 * d->n_groups ? d->hyper[k] : 0.f;
+    return launch_adamw_groups<true>(d, hv, st, (long long)n_norm);
 }
 
 }  // extern "C"

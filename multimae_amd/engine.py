@@ -302,15 +302,27 @@ class ParamArena:
     ``groups``: name prefixes in the order the backward pass finishes their gradients (for MultiMAE: output adapters,
     encoder.L-1 ... encoder.0); parameters are laid out group by group, everything not named by a prefix last (the
     ``tail``: input adapters + global token, whose gradients are final only when backward ends).  A data-parallel reducer then
-    sees contiguous ranges complete one after another (dist.GradAllReducer).  state_dict() order is unaffected."""
+    sees contiguous ranges complete one after another (dist.GradAllReducer).  state_dict() order is unaffected.
 
-    def __init__(self, module: nn.Module, device: Optional[torch.device] = None, groups: Optional[List[str]] = None):
+    ``extra``: ``[(name, parameter)]`` of trainable tensors that are NOT the module's (the loss balancer's ``log_vars``, as
+    ``balancer.log_vars``): appended after the module's own trainable tensors -- the END of the trainable prefix, each in a
+    64-element chunk of its own -- and listed after the module's names in ``param_order``.  The optimiser and the reducer then
+    cover them with the rest; the owners' ``state_dict()`` do not change."""
+
+    def __init__(self, module: nn.Module, device: Optional[torch.device] = None, groups: Optional[List[str]] = None,
+                 extra: Optional[List] = None):
         params = [(n, p) for n, p in module.named_parameters()]
         if not params:
             raise ValueError('module has no parameters')
+        extra = [(n, p) for n, p in (extra or [])]
+        own = {n for n, _ in params}
+        for n, p in extra:
+            if n in own or not p.requires_grad or any(p is q for _, q in params):
+                raise ValueError(f'ParamArena(extra=...): {n} must be a trainable tensor outside the module, under a name of its own')
+        self.extra_names: List[str] = [n for n, _ in extra]
         # registration order (named_parameters()): what torch.optim state dicts index by -- the arena layout below is the
         # backward-readiness order and must never leak into a checkpoint (checkpoint.py iterates param_order)
-        self.param_order: List[str] = [n for n, _ in params]
+        self.param_order: List[str] = [n for n, _ in params] + self.extra_names
         self._tail: List[str] = []
         if groups:
             taken, ordered_all = set(), []
@@ -329,7 +341,9 @@ class ParamArena:
         self.sizes: Dict[str, int] = {}
         self.trainable: Dict[str, bool] = {}
         # trainable tensors first (so optimiser / all-reduce touch one contiguous prefix)
-        ordered = [(n, p) for n, p in params if p.requires_grad] + [(n, p) for n, p in params if not p.requires_grad]
+        ordered = [(n, p) for n, p in params if p.requires_grad] + extra + [(n, p) for n, p in params if not p.requires_grad]
+        if self._tail:
+            self._tail += self.extra_names                # part of the last bucket: final as soon as backward starts, which is harmless
         off = 0
         for n, p in ordered:
             self.names.append(n)

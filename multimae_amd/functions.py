@@ -157,6 +157,16 @@ class GradSink:
             return None
         return g.reshape(p.shape)
 
+    def vec_dest(self, p: Tensor):
+        """``vec`` for a kernel that writes the gradient itself: (destination f32 tensor of p's shape, accumulate flag, bound).
+        Direct mode with an arena-bound p.grad: the gradient view -- stored into when this is the parameter's first write since
+        ``zero_grad()`` (engine.claim_first_write), added to otherwise -- and the caller returns None to autograd.  Else a fresh
+        tensor to hand back.  The caller launches on the current stream: for a tensor no other node writes."""
+        if self.direct and _bound_grad(p) is not None:
+            fresh = engine.claim_first_write([p])       # (marks p written)
+            return p.grad, not fresh, True
+        return torch.empty(p.shape, device=p.device, dtype=torch.float32), False, False
+
 
 def _new(shape, like: Tensor, dtype):
     return torch.empty(shape, device=like.device, dtype=dtype)
@@ -1904,3 +1914,37 @@ class DPTHeadFn(torch.autograd.Function):
         g1w, g1b = _conv_wgrad(sink, c1w, dwp1), sink.bias(c1b, dt1.view(-1, Ch))
         ctx.saved = ctx.params = None
         return (None, (dx.permute(0, 3, 1, 2) if dx is not None else None), g1w, g1b, g2w, g2b, gtw, gtb)
+
+
+# ------------------------------------------------------------------------------------------
+# uncertainty task balancer (utils/task_balancing.py:21-44): one node over the T scalar losses and log_vars
+# ------------------------------------------------------------------------------------------
+class TaskBalanceFn(torch.autograd.Function):
+    """``TaskBalanceFn.apply(log_vars, *losses) -> T scalars`` w_i = (exp(-s_i) L_i + s_i) (L_i != 0): one launch forward, one
+    backward (csrc/balance.hip).  The outputs are the T elements of one buffer; the T upstream gradients are read through their
+    own pointers, so nothing is stacked or unbound on the way.  Direct-gradient mode: d log_vars goes into the arena-bound
+    ``log_vars.grad`` (GradSink.vec_dest) and autograd receives None for it."""
+
+    @staticmethod
+    def forward(ctx, log_vars: Tensor, *losses: Tensor):
+        T = len(losses)
+        lv = log_vars.detach()
+        weighted = torch.empty(T, device=lv.device, dtype=torch.float32)
+        saved = torch.empty(2 * T, device=lv.device, dtype=torch.float32)
+        ops.task_balance_fwd([l.detach() for l in losses], lv, weighted, saved)
+        ctx.log_vars, ctx.saved, ctx.T = log_vars, saved, T
+        ctx.set_materialize_grads(False)
+        return tuple(weighted[i] for i in range(T))
+
+    @staticmethod
+    def backward(ctx, *ups):
+        T, p = ctx.T, ctx.log_vars
+        d_losses = torch.empty(T, device=ctx.saved.device, dtype=torch.float32)
+        bound = False
+        if p.requires_grad:
+            dst, acc, bound = GradSink(engine.direct_grads()).vec_dest(p)
+        else:
+            dst, acc = torch.empty(T, device=ctx.saved.device, dtype=torch.float32), False
+        ops.task_balance_bwd([u.detach() if u is not None else None for u in ups], ctx.saved, d_losses, dst, acc)
+        d_lv = None if (bound or not p.requires_grad) else dst
+        return (d_lv,) + tuple(d_losses[i] if ctx.needs_input_grad[1 + i] else None for i in range(T))

@@ -102,9 +102,14 @@ class MultiMAE(nn.Module):
         return no_wd_set
 
     # -- engine management ------------------------------------------------------------------
-    def build_arena(self) -> 'engine.ParamArena':
-        """Move every parameter into one flat HBM arena (idempotent; call after .to(device))."""
+    def build_arena(self, extra=None) -> 'engine.ParamArena':
+        """Move every parameter into one flat HBM arena (idempotent; call after .to(device)).  ``extra``: ``{prefix: module}`` whose
+        trainable parameters join the arena after the model's own as ``prefix.name`` (the loss balancer: ``{'balancer': balancer}``,
+        engine.ParamArena(extra=...)); an arena built without them is rebuilt -- before the optimiser is created."""
         a = engine.arena_of(self)
+        extra_params = [(f'{pre}.{n}', p) for pre, m in (extra or {}).items() for n, p in m.named_parameters() if p.requires_grad]
+        if a is not None and extra_params and not all(a._params.get(n) is p for n, p in extra_params):
+            a = None
         if a is None:
             # gradient-readiness order (see engine.ParamArena): autograd runs the output adapters' backward in reverse
             # forward order, then the encoder from its last block down; the embedding gradients come last
@@ -112,7 +117,7 @@ class MultiMAE(nn.Module):
             if self.output_adapters is not None:
                 groups += [f'output_adapters.{d}.' for d in reversed(list(self.output_adapters))]
             groups += [f'encoder.{l}.' for l in reversed(range(len(self.encoder)))]
-            a = engine.ParamArena(self, groups=groups)
+            a = engine.ParamArena(self, groups=groups, extra=extra_params)
         return a
 
     # -- mask sampling ----------------------------------------------------------------------

@@ -1477,11 +1477,16 @@ def opt_step_groups(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, i
                     n_groups: int, hyper: Optional[Sequence[float]] = None, hyper_dev: Optional[Tensor] = None, beta1: float,
                     beta2: float, eps: float, clip_grad: Optional[float], skip_grad: Optional[float], grad_prescale: float = 1.0,
                     loss_dev: Optional[Tensor] = None, shadow: Optional[Tensor] = None, found_inf_dev: Optional[Tensor] = None,
-                    grad_scale_dev: Optional[Tensor] = None) -> None:
+                    grad_scale_dev: Optional[Tensor] = None, n_norm: Optional[int] = None) -> None:
     """mmae_opt_step_groups: opt_step with a (lr, weight_decay) per parameter group.  ``group_map``: int16 (read as uint16)
     [ceil(n / 64)], the group of every 64-element chunk.  ``hyper``: host [lr_0, wd_0, lr_1, wd_1, ...], passed to the launch by
-    value (at most OPT_MAX_GROUPS groups); ``hyper_dev``: the same as a device f32 [n_groups, 2] tensor (hipGraph replay)."""
+    value (at most OPT_MAX_GROUPS groups); ``hyper_dev``: the same as a device f32 [n_groups, 2] tensor (hipGraph replay).
+    ``n_norm`` (mmae_opt_step_groups_tail): the gradient norm, the clip and the skip decisions cover ``g[:n_norm]`` only, and
+    ``g[n_norm:]`` is applied unclipped -- the parameters the loop does not hand to the loss scaler (the task balancer's)
+    -- with ``state[7]`` the scale they took; a positive multiple of 64, at most ``p.numel()``."""
     n = p.numel()
+    if n_norm is not None and not (0 < n_norm <= n and n_norm % 64 == 0):
+        raise ValueError(f'opt_step_groups: n_norm = {n_norm} must be a positive multiple of 64, at most n = {n}')
     assert group_map.dtype == torch.int16 and group_map.numel() == (n + 63) // 64, 'group_map: int16 [ceil(n / 64)]'
     assert (hyper is None) != (hyper_dev is None), 'give exactly one of hyper / hyper_dev'
     assert state.dtype == torch.float32 and state.numel() >= 8 and istate.dtype == torch.int32 and istate.numel() >= 8
@@ -1501,7 +1506,61 @@ def opt_step_groups(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, i
         assert len(hyper) == 2 * n_groups and n_groups <= _lib.OPT_MAX_GROUPS
         host = (ctypes.c_float * len(hyper))(*hyper)       # copied into the launch's arguments during the call
         d.hyper = ctypes.addressof(host)
+    if n_norm is not None:
+        check(_lib.load().mmae_opt_step_groups_tail(ctypes.byref(d), int(n_norm), _stream()), 'opt_step_groups_tail')
+        return
     check(_lib.load().mmae_opt_step_groups(ctypes.byref(d), _stream()), 'opt_step_groups')
+
+
+# ----------------------------------------------------------------- task balancer (csrc/balance.hip) --
+BALANCE_MAX_TASKS = 16     # MMAE_BALANCE_MAX_TASKS
+
+
+def _scalar_ptrs(ts: Sequence[Optional[Tensor]], dev, what: str):
+    """host array of device pointers to f32 scalars (None -> null), and the tensors kept alive for the call"""
+    keep = []
+    for t in ts:
+        if t is None:
+            keep.append(None)
+            continue
+        if t.numel() != 1 or t.device != dev:
+            raise ValueError(f'{what}: every entry is a one-element tensor on {dev}')
+        if t.dtype != torch.float32:
+            t = t.float()
+        keep.append(t)
+    arr = (ctypes.c_void_p * len(keep))(*[(t.data_ptr() if t is not None else None) for t in keep])
+    return arr, keep
+
+
+def task_balance_fwd(losses, log_vars: Tensor, weighted: Tensor, saved: Tensor) -> None:
+    """mmae_task_balance_fwd.  ``losses``: a sequence of T one-element device tensors (read through T pointers, no stack) or a
+    packed f32 [T] tensor; ``weighted`` f32 [T], ``saved`` f32 [2 T] (exp(-log_vars), then the losses)."""
+    T = log_vars.numel()
+    assert weighted.numel() == T and saved.numel() == 2 * T and weighted.dtype == saved.dtype == log_vars.dtype == torch.float32
+    if isinstance(losses, Tensor):
+        assert losses.dtype == torch.float32 and losses.numel() == T and losses.is_contiguous()
+        arr, packed = None, losses.data_ptr()
+    else:
+        assert len(losses) == T
+        (arr, keep), packed = _scalar_ptrs(losses, log_vars.device, 'task_balance_fwd'), None
+    check(_lib.load().mmae_task_balance_fwd(arr, packed, log_vars.data_ptr(), weighted.data_ptr(), saved.data_ptr(), T, _stream()),
+          'task_balance_fwd')
+
+
+def task_balance_bwd(upstream, saved: Tensor, d_losses: Tensor, d_log_vars: Tensor, accumulate: bool) -> None:
+    """mmae_task_balance_bwd.  ``upstream``: a sequence of T one-element device tensors / None (no gradient: 0) or a packed f32
+    [T] tensor; ``d_log_vars`` is stored, or added to when ``accumulate``."""
+    T = d_losses.numel()
+    assert saved.numel() == 2 * T and d_log_vars.numel() == T and d_losses.dtype == d_log_vars.dtype == saved.dtype == torch.float32
+    assert d_log_vars.is_contiguous() and d_losses.is_contiguous()
+    if isinstance(upstream, Tensor):
+        assert upstream.dtype == torch.float32 and upstream.numel() == T and upstream.is_contiguous()
+        arr, packed = None, upstream.data_ptr()
+    else:
+        assert len(upstream) == T
+        (arr, keep), packed = _scalar_ptrs(upstream, saved.device, 'task_balance_bwd'), None
+    check(_lib.load().mmae_task_balance_bwd(arr, packed, saved.data_ptr(), d_losses.data_ptr(), d_log_vars.data_ptr(), int(bool(accumulate)), T,
+                                            _stream()), 'task_balance_bwd')
 
 
 # ------------------------------------------------------------------ ConvNeXt head (csrc/convnext.hip) --

@@ -47,12 +47,16 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def __init__(self, model: nn.Module, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.95), eps: float = 1e-8,
                  weight_decay: float = 0.05, clip_grad: Optional[float] = None, skip_grad: Optional[float] = None,
-                 groups: Optional[List[dict]] = None):
+                 groups: Optional[List[dict]] = None, norm_exempt: Optional[List[torch.Tensor]] = None):
         """``groups``: torch-style param group dicts over the arena's trainable tensors (``params`` plus ``weight_decay``,
         ``lr_scale`` and optionally ``lr``; the output of the reference's ``get_parameter_groups``, utils/optim_factory.py:51-101,
         or ``dropin.amd_loop.create_optimizer_groups``).  Every trainable tensor must be in exactly one group, and all groups
         share ``betas`` / ``eps``.  ``step()`` then runs mmae_opt_step_groups: one gradient norm over the whole arena, each
-        group's own ``lr`` / ``weight_decay``.  Without ``groups``: the one group of the pre-training recipe (mmae_opt_step)."""
+        group's own ``lr`` / ``weight_decay``.  Without ``groups``: the one group of the pre-training recipe (mmae_opt_step).
+        ``norm_exempt`` (with ``groups``): parameters the loop does not hand to the loss scaler -- the task balancer's ``log_vars``,
+        run_pretraining_multimae.py:536-537 passes ``parameters=model.parameters()`` -- so their gradient enters neither the norm
+        nor the clip (mmae_opt_step_groups_tail); ``grad_norm`` is then the model-only norm.  They must be the arena's LAST
+        trainable tensors (engine.ParamArena(extra=...)), otherwise ValueError."""
         self.arena = engine.arena_of(model) or engine.ParamArena(model)
         a = self.arena
         n = a.n_trainable
@@ -68,6 +72,7 @@ class FusedAdamW(torch.optim.Optimizer):
             if len({(tuple(g['betas']), g['eps']) for g in self.param_groups}) != 1:
                 raise ValueError('FusedAdamW(groups=...): all groups must share betas and eps (one fused step)')
             self._group_map = self._chunk_map()
+        self.n_norm: Optional[int] = self._norm_prefix(norm_exempt) if norm_exempt else None
         self.m = torch.zeros(n, device=a.device, dtype=torch.float32)
         self.v = torch.zeros(n, device=a.device, dtype=torch.float32)
         self.clip_grad, self.skip_grad = clip_grad, skip_grad
@@ -113,6 +118,26 @@ class FusedAdamW(torch.optim.Optimizer):
         if missing:
             raise ValueError(f'FusedAdamW(groups=...): {len(missing)} trainable tensors are in no group, e.g. {missing[0]}')
         return out, names
+
+    def _norm_prefix(self, exempt) -> int:
+        """Elements of the gradient arena the norm covers: everything before the exempt tensors, which must end the trainable prefix."""
+        a = self.arena
+        if self._group_map is None:
+            raise ValueError('FusedAdamW(norm_exempt=...) needs groups=... (the exempt tensors are a param group of their own)')
+        name_of = {id(p): nm for nm, p in a._params.items()}
+        names = set()
+        for p in exempt:
+            nm = name_of.get(id(p))
+            if nm is None or not a.trainable[nm]:
+                raise ValueError(f'FusedAdamW(norm_exempt=...): a tensor of shape {tuple(p.shape)} is not a trainable tensor of the arena')
+            names.add(nm)
+        n_norm = min(a.offsets[nm] for nm in names)
+        behind = {nm for nm in a.names if a.trainable[nm] and a.offsets[nm] >= n_norm}
+        if behind != names or n_norm == 0:
+            other = sorted(behind - names)
+            raise ValueError('FusedAdamW(norm_exempt=...): the exempt tensors must be the last trainable tensors of the arena'
+                             + (f' ({other[0]} lies behind {sorted(names)[0]})' if other else ' and leave a tensor for the norm'))
+        return n_norm
 
     def _chunk_map(self) -> torch.Tensor:
         """int16 [n_trainable / 64]: the group of every 64-element chunk of the arena (engine.ALIGN keeps tensors apart)."""
@@ -209,7 +234,7 @@ class FusedAdamW(torch.optim.Optimizer):
             ops.opt_step_groups(a.param[:n], a.grad, self.m, self.v, self._state, self._istate, self._ws, group_map=self._group_map,
                                 n_groups=len(self.param_groups), hyper=hyper, hyper_dev=hyper_dev, beta1=b1, beta2=b2, eps=g['eps'],
                                 clip_grad=self.clip_grad, skip_grad=self.skip_grad, grad_prescale=self.grad_prescale, loss_dev=loss,
-                                shadow=shadow, found_inf_dev=found_inf, grad_scale_dev=grad_scale)
+                                shadow=shadow, found_inf_dev=found_inf, grad_scale_dev=grad_scale, n_norm=self.n_norm)
         if shadow is not None:
             a.mark_shadow_fresh()
         if cap is None and a.param.is_cuda and self.max_steps_in_flight:

@@ -14,7 +14,9 @@ What it shows: argument parsing, ``utils.create_model('pretrain_multimae_base', 
 reference's own registry, the DOMAIN_CONF adapters / criteria, ``create_optimizer``'s dict branch, ``NativeScaler``, the cosine tables,
 ``train_one_epoch`` with its MetricLogger, and the epoch loop all run against the engine's classes without a line of the script changed.
 With ``--patched`` the same run on a temporary copy of the script with ``dropin/run_pretraining_multimae.patch`` applied
-(``amd_loop.wrap_model`` / ``create_optimizer`` / ``LossScaler``).
+(``amd_loop.task_balancer`` / ``wrap_model`` / ``create_optimizer`` / ``LossScaler``).  ``--task_balancer uncertainty`` runs the
+script with that option and three output tasks (the balancer has one log-variance per entry of ``--out_domains``, so the fourth
+loss of ``--extra_norm_pix_loss`` is left out).
 
     PYTHONDONTWRITEBYTECODE=1 python tools/run_reference_script_dryrun.py [--patched] > profiles/r05_reference_script_dryrun[_patched].log
 """
@@ -31,6 +33,7 @@ import types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = '/root/reference'
 PATCHED = '--patched' in sys.argv
+BALANCER = sys.argv[sys.argv.index('--task_balancer') + 1] if '--task_balancer' in sys.argv else 'none'
 
 import torch  # noqa: E402
 
@@ -120,6 +123,9 @@ if PATCHED:
 sys.argv = [script, '--device', 'cpu', '--batch_size', str(BATCH), '--epochs', '2', '--warmup_epochs', '1', '--num_workers', '0',
             '--in_domains', 'rgb-depth-semseg', '--out_domains', 'rgb-depth-semseg', '--extra_norm_pix_loss', '--no_loss_on_unmasked',
             '--fp32_output_adapters', 'semseg', '--no_standardize_depth', '--no_auto_resume', '--output_dir', '', '--model', 'pretrain_multimae_base']
+if BALANCER != 'none':
+    sys.argv[sys.argv.index('--extra_norm_pix_loss')] = '--no_extra_norm_pix_loss'
+    sys.argv += ['--task_balancer', BALANCER, '--balancer_lr_scale', '10']
 print(f'[dryrun] running {"the PATCHED copy of " if PATCHED else "the UNMODIFIED "}{os.path.join(REF, "run_pretraining_multimae.py")}: ' + ' '.join(sys.argv[1:]))
 import multimae  # noqa: E402
 print('[dryrun] `multimae` resolves to', os.path.dirname(multimae.__file__))
