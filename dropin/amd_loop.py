@@ -321,6 +321,36 @@ def mixup(args):
                    num_classes=args.nb_classes)
 
 
+def random_erasing(args):
+    """Replaces the ``RandomErasing(re_prob, mode=re_mode, max_count=re_count, num_splits=re_num_splits, device='cpu')`` that
+    ``create_transform`` appends to the training transform (utils/transforms_factory.py:127-129) from ``--reprob / --remode /
+    --recount``: the engine's ``multimae_amd.RandomErasing``, applied to the batch on the device, or None when ``--reprob`` is 0."""
+    reprob = getattr(args, 'reprob', 0.)
+    if not reprob or reprob <= 0.:
+        return None
+    return M.RandomErasing(probability=reprob, mode=getattr(args, 'remode', 'pixel'), max_count=getattr(args, 'recount', 1),
+                           num_splits=0, device='cuda')
+
+
+def cls_staged_loader(data_loader, args, device=None, train=True, erase_float32=True):
+    """Wraps a classification DataLoader in ``multimae_amd.ClsStagedLoader``: it yields ``(samples, targets)`` on the device, every
+    batch copied on the stager's stream one step ahead.  With a transform that ends in the reference's prefetch form (``ToNumpy()``:
+    uint8 (3, H, W)) the batch is copied as bytes and normalised -- and, for the training loader, erased per
+    ``--reprob / --remode / --recount`` -- there in one launch.  float32 batches are copied as they are and, for the training loader,
+    erased in place: that is right only when the host transform does NOT erase (``create_transform(..., re_prob=0.)``).  The
+    UNCHANGED ``build_transform`` passes ``re_prob=args.reprob`` and so already ends in ``RandomErasing(device='cpu')``
+    (utils/datasets.py:177, utils/transforms_factory.py:127-129): with it pass ``erase_float32=False``, which only moves the copy
+    off the compute stream, or every sample is erased twice.  The loop's ``.to(device, non_blocking=True)``
+    (run_finetuning_cls.py:510-511, :593-594) becomes a no-op."""
+    from multimae_amd import staging
+    default = getattr(args, 'imagenet_default_mean_and_std', True)
+    mean = staging.IMAGENET_DEFAULT_MEAN if default else staging.IMAGENET_INCEPTION_MEAN
+    std = staging.IMAGENET_DEFAULT_STD if default else staging.IMAGENET_INCEPTION_STD
+    device = torch.device(device if device is not None else getattr(args, 'device', 'cuda'))
+    stager = staging.ClsStager(device, mean, std, random_erasing=random_erasing(args) if train else None, erase_float32=erase_float32)
+    return staging.ClsStagedLoader(data_loader, stager)
+
+
 def cls_criterion(args, mixup_fn=None):
     """Replaces the criterion choice of run_finetuning_cls.py:403-409: soft targets under mixup (the smoothing is in the target),
     label smoothing without it, plain cross-entropy (``torch.nn.CrossEntropyLoss``, as the script) when both are off."""

@@ -986,6 +986,38 @@ int mmae_ingest_rgb_u8(const uint8_t* x, const float* table, float* y, int B, in
 int mmae_ingest_depth(const void* x, int x_dtype, float* y, int B, int n, int standardize, int lo, int hi, float eps, void* stream);
 int mmae_ingest_semseg_u8(const uint8_t* x, int64_t* y, int B, int n, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Random erasing (csrc/erase.hip; multimae_amd/random_erasing.py, staging.ClsStager): RandomErasing.__call__ / _erase
+ * (utils/random_erasing.py:74-103), the last step of the classification training transform ToTensor -> Normalize ->
+ * RandomErasing (utils/transforms_factory.py:117-129), on the device.  Every random choice of the reference is made on the
+ * host, in its order, and arrives as one table.
+ *   table   int32 [B + 1][MMAE_ERASE_ROW] on the device.
+ *           row 0      the call's header: words 0-1 the 64-bit noise seed (low, high), words 2-3 the 64-bit call counter
+ *                      (low, high), word 4 the mode (0 'const', 1 'rand', 2 'pixel'), the rest 0.
+ *           row 1 + b  sample b: word 0 = n, the number of rectangles, in [0, MMAE_ERASE_MAX_RECTS]; words 1-3 = 0;
+ *                      rectangle r at words 4 + 8 r: top, left, h, w, then the bits of the f32 colours of channels 0-3 (read
+ *                      in 'rand' mode only; a channel beyond 3 takes colour 3).
+ *   pixel   (y, x) of sample b is erased when it lies in [top, top + h) x [left, left + w) of one of its rectangles; where
+ *           several overlap the highest r gives the value.  h == 0 or w == 0 erases nothing.  The rectangles must lie inside
+ *           the image; the kernels intersect each one with it -- rows [max(top, 0), min(top + h, H)), likewise the columns; a
+ *           negative h or w counts as 0 -- and take n as at most the maximum, so nothing is ever written outside the tensor.
+ *   value   'const' 0; 'rand' the rectangle's colour of the channel; 'pixel' a standard normal that depends only on the
+ *           header and on the element's linear index e in the contiguous f32 [B][C][H][W] tensor: Philox4x32-10 (multipliers
+ *           0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with key (seed low, seed high) and counter
+ *           (low32(e >> 2), high32(e >> 2), counter low, counter high) gives o0..o3; with p = (e & 3) >> 1,
+ *           u1 = ((o[2p] >> 8) + 1) 2^-24, u2 = (o[2p + 1] >> 8) 2^-24, r = sqrtf(-2 logf(u1)), the value is r cospif(2 u2) for
+ *           even e and r sinpif(2 u2) for odd e.
+ * mmae_random_erase: x f32 [B][C][H][W] in place; writes erased pixels only and touches no other byte of x.
+ * mmae_ingest_rgb_u8_chw_erase: x uint8 [B][3][H][W] (the prefetch form: ToNumpy + the default collate), lut f32 [3][256] as
+ * for mmae_ingest_rgb_u8; y f32 [B][3][H][W] = erased ? value : lut[c][x], every element written exactly once.  table == NULL
+ * decodes without erasing.  It equals the decode followed by mmae_random_erase with the same table bit for bit, in every mode.
+ * ------------------------------------------------------------------------- */
+#define MMAE_ERASE_MAX_RECTS 8
+#define MMAE_ERASE_ROW 68            /* int32 words per table row: 4 + 8 * MMAE_ERASE_MAX_RECTS */
+int mmae_random_erase(float* x, const int32_t* table, int B, int C, int H, int W, void* stream);
+int mmae_ingest_rgb_u8_chw_erase(const uint8_t* x, const float* lut, const int32_t* table, float* y,
+                                 int B, int H, int W, void* stream);
+
 /* hardware probes used by tests/ to pin instruction semantics the kernels rely on */
 /* SemSegInputAdapter(interpolate_class_emb=True) (input_adapters.py:192-198): the class-embedding image resized by 1 / patch with
  * nn.Upsample(bilinear) -- per token the mean of the centre taps -- as out f32 [B][E][H/ph][W/pw] (then projected like a 1 x 1 patch

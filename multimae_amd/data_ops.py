@@ -87,6 +87,49 @@ def ingest_semseg_u8(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------- random erasing (csrc/erase.hip) --
+# The table is RandomErasing.draw()'s (multimae_amd/random_erasing.py; layout in include/mmae.h, "Random erasing").
+
+ERASE_ROW_WORDS = _lib.ERASE_ROW
+
+
+def _erase_table(table, B: int, device, what: str) -> None:
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or tuple(table.shape) != (B + 1, ERASE_ROW_WORDS) \
+            or not table.is_contiguous() or table.device != device:
+        got = f'{tuple(table.shape)} {table.dtype} on {table.device}' if torch.is_tensor(table) else type(table).__name__
+        raise ValueError(f'{what}: table must be a contiguous int32 ({B + 1}, {ERASE_ROW_WORDS}) tensor on {device}, got {got}')
+
+
+def random_erase_(x: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """Erases the rectangles of ``table`` in the contiguous f32 (B, C, H, W) batch ``x`` in place; only erased pixels are touched."""
+    ops._require_gpu(x, 'x')
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f'random_erase_: expected a contiguous non-empty (B, C, H, W) float32 batch, got {tuple(x.shape)} {x.dtype}')
+    B, C, H, W = x.shape
+    _erase_table(table, B, x.device, 'random_erase_')
+    _lib.check(_lib.load().mmae_random_erase(x.data_ptr(), table.data_ptr(), B, C, H, W, ops._stream()), 'random_erase')
+    return x
+
+
+def ingest_rgb_u8_chw(x: torch.Tensor, lut: torch.Tensor, table: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+    """(B, 3, H, W) uint8 CHW (``ToNumpy`` + the default collate) -> (B, 3, H, W) f32: ``out[b, c, h, w] = lut[c, x[b, c, h, w]]``
+    (``lut`` from ``rgb_table``, on the device), except where a rectangle of ``table`` erases it -- bit-identical to
+    ``random_erase_`` of the lookup.  ``table=None`` decodes only."""
+    ops._require_gpu(x, 'rgb')
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise ValueError(f'ingest_rgb_u8_chw: expected a non-empty (B, 3, H, W) uint8 batch, got {tuple(x.shape)} {x.dtype}')
+    if lut.dtype != torch.float32 or lut.shape != (3, 256) or not lut.is_contiguous() or lut.device != x.device:
+        raise ValueError('ingest_rgb_u8_chw: lut must be a contiguous f32 (3, 256) tensor on the input\'s device')
+    B, _, H, W = x.shape
+    if table is not None:
+        _erase_table(table, B, x.device, 'ingest_rgb_u8_chw')
+    x = x.contiguous()
+    out = _out(out, (B, 3, H, W), torch.float32, x.device, 'ingest_rgb_u8_chw')
+    _lib.check(_lib.load().mmae_ingest_rgb_u8_chw_erase(x.data_ptr(), lut.data_ptr(), None if table is None else table.data_ptr(),
+                                                        out.data_ptr(), B, H, W, ops._stream()), 'ingest_rgb_u8_chw_erase')
+    return out
+
+
 def depth_standardize_(x: torch.Tensor, lo: float = 0.1, hi: float = 0.9, eps: float = 1e-6) -> torch.Tensor:
     """``truncated_depth_standardize`` in place, on a contiguous f32 (B, ...) map (the kernel allows y to alias x)."""
     ops._require_gpu(x, 'depth')

@@ -15,6 +15,9 @@ Forms accepted per task (anything else raises ``ValueError``):
 
 Depth comes out as (B, 1, H, W) f32, standardised on the copy stream when ``standardize_depth=(lo, hi, eps)`` (in the decode
 launch for the compact form); the training loop must then not standardise it again.
+
+``ClsStager`` / ``ClsStagedLoader`` (end of the file) do the same for the ``(images, target)`` batches of classification
+fine-tuning: uint8 (B, 3, H, W) images normalised and randomly erased by one launch on the copy stream (csrc/erase.hip).
 """
 from __future__ import annotations
 
@@ -165,15 +168,21 @@ class BatchStager:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError('BatchStager.stage: not allowed inside a graph capture (stage between replays, with into=)')
         forms = batch_forms(batch)
+        specs = {task: _out_spec(task, t, forms[task]) for task, t in batch.items()}
+        return self._queue('BatchStager', batch, forms, specs, into, after)
+
+    def _queue(self, who: str, batch, forms, specs, into, after) -> StagedBatch:
+        """The part of ``stage`` that does not depend on what a batch holds: ``specs`` is task -> (shape, dtype) of the staged
+        tensor."""
         for task, t in batch.items():
             if t.is_cuda:
-                raise ValueError(f'BatchStager: task {task!r} is already on {t.device}; the stager copies host batches')
+                raise ValueError(f'{who}: task {task!r} is already on {t.device}; the stager copies host batches')
         if into is not None:
             for task, t in batch.items():
-                shape, dtype = _out_spec(task, t, forms[task])
+                shape, dtype = specs[task]
                 o = into.get(task)
                 if o is None or tuple(o.shape) != shape or o.dtype != dtype or o.device != self.device or not o.is_contiguous():
-                    raise ValueError(f'BatchStager: into[{task!r}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}')
+                    raise ValueError(f'{who}: into[{task!r}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}')
         self._release()
         host = {task: t.contiguous() for task, t in batch.items()}
         pageable = [task for task, t in host.items() if not t.is_pinned()]
@@ -184,21 +193,23 @@ class BatchStager:
                 self._slot_event[slot].synchronize()          # the slot's previous H2D has completed
             for task in pageable:
                 host[task] = self._pinned(slot, task, host[task])
-        out = {}
+        out, hold = {}, []                         # hold: further host tensors a subclass's _stage_one copies from
         with torch.cuda.stream(self.stream):
             if after is not None:
                 self.stream.wait_event(after)
             for task, h in host.items():
                 o = None if into is None else into[task]
-                out[task] = self._stage_one(task, h, forms[task], o)
+                out[task] = self._stage_one(task, h, forms[task], o, hold)
             event = torch.cuda.Event()
             event.record(self.stream)
         if slot is not None:
             self._slot_event[slot] = event
-        self._held.append((event, list(batch.values()) + list(host.values())))
+        self._held.append((event, list(batch.values()) + list(host.values()) + hold))
         return StagedBatch(out, event, into is None)
 
-    def _stage_one(self, task, h, form, o):
+    def _stage_one(self, task, h, form, o, hold):
+        """Copy (and decode) one task's pinned host tensor ``h`` on the copy stream, into ``o`` when given.  A host tensor made here and
+        copied from without blocking is appended to ``hold``: it is kept until the batch's event has completed."""
         kind = _kind(task)
         if form == 'reference':
             d = torch.empty(h.shape, dtype=h.dtype, device=self.device) if o is None else o
@@ -268,3 +279,118 @@ class StagedLoader:
             yield self._get(cur)
             cur = nxt
         yield self._get(cur)
+
+
+# ------------------------------------------------------------------------------------------ classification fine-tuning --
+# run_finetuning_cls.py moves (samples, targets) with ``.to(device, non_blocking=True)`` on the compute stream, the samples already
+# normalised and erased on the host (ToTensor -> Normalize -> RandomErasing, utils/transforms_factory.py:117-129): 77 MB per batch
+# of 128 at 224 x 224.  With the reference's own prefetch form (``create_transform(use_prefetcher=True)`` ends in ``ToNumpy()``:
+# uint8 (3, H, W)) 19 MB cross PCIe, and one launch on the copy stream normalises and erases (csrc/erase.hip).
+
+def cls_form(images) -> str:
+    """'compact' (uint8 (B, 3, H, W), the prefetch form) or 'reference' (float32 (B, 3, H, W)); ``ValueError`` otherwise."""
+    if torch.is_tensor(images):
+        s, d = tuple(images.shape), images.dtype
+        if len(s) == 4 and s[1] == 3 and all(v > 0 for v in s) and d in (torch.uint8, torch.float32):
+            return 'compact' if d == torch.uint8 else 'reference'
+        got = f'shape {s}, dtype {d}'
+    else:
+        got = type(images).__name__
+    raise ValueError(f'ClsStager: images: {got} is neither the prefetch form (uint8 (B, 3, H, W)) nor the reference form '
+                     f'(float32 (B, 3, H, W)), or is empty')
+
+
+class ClsStager(BatchStager):
+    """``BatchStager`` for the classification loop's ``(images, target)`` batches: same pinned slots, copy stream, held host
+    tensors, ready event and ``into=`` / ``after=`` contract.
+
+      images   uint8 (B, 3, H, W)    copied as bytes, then normalised and erased by one ``mmae_ingest_rgb_u8_chw_erase`` launch
+               float32 (B, 3, H, W)  copied as it is, then erased in place when ``random_erasing`` is given and ``erase_float32``
+      target   any tensor of B rows (labels), copied alongside
+
+    ``random_erasing``: a ``multimae_amd.RandomErasing`` whose ``draw()`` is called once per staged batch, at stage time (so in the
+    order the batches are staged); None (the evaluation loader) decodes only.
+    ``erase_float32``: a float32 batch comes from a host transform that has already normalised it.  If that transform also ends in
+    the reference's ``RandomErasing(device='cpu')`` -- ``create_transform`` appends it whenever ``re_prob > 0``
+    (utils/transforms_factory.py:127-129) -- erasing here would erase every sample a second time: pass ``erase_float32=False`` then,
+    and float32 batches are only copied (no table is drawn for them).  uint8 batches are erased either way."""
+
+    def __init__(self, device=None, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, random_erasing=None, erase_float32=True):
+        super().__init__(device, mean, std)
+        self.random_erasing = random_erasing
+        self.erase_float32 = bool(erase_float32)
+
+    def bytes_per_batch(self, batch) -> Dict[str, int]:
+        images, target = self._pair(batch)
+        inp, out = _nbytes(images.shape, images.dtype), _nbytes(images.shape, torch.float32)
+        tgt = _nbytes(target.shape, target.dtype)
+        compact = cls_form(images) == 'compact'
+        return {'h2d': inp + tgt, 'device': out + tgt, 'hbm': inp + out if compact else 0}
+
+    @staticmethod
+    def _pair(item):
+        if not (isinstance(item, (tuple, list)) and len(item) == 2):
+            raise ValueError(f'ClsStager: a batch is an (images, target) pair, got {type(item).__name__}')
+        images, target = item
+        cls_form(images)
+        if not torch.is_tensor(target) or target.dim() < 1 or target.shape[0] != images.shape[0]:
+            got = f'shape {tuple(target.shape)}, dtype {target.dtype}' if torch.is_tensor(target) else type(target).__name__
+            raise ValueError(f'ClsStager: target: {got} is not a tensor of {images.shape[0]} rows')
+        return images, target
+
+    def stage(self, item, into=None, after: Optional[torch.cuda.Event] = None) -> StagedBatch:
+        """Queue one ``(images, target)`` batch.  ``into``: a caller-owned ``(x, target)`` pair of static device tensors to write
+        instead of new ones; the copy stream first waits on ``after`` (``BatchStager.stage``)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ClsStager.stage: not allowed inside a graph capture (stage between replays, with into=)')
+        images, target = self._pair(item)
+        batch = {'images': images, 'target': target}
+        forms = {'images': cls_form(images), 'target': 'reference'}
+        specs = {'images': (tuple(images.shape), torch.float32), 'target': (tuple(target.shape), target.dtype)}
+        if into is not None:
+            if not (isinstance(into, (tuple, list)) and len(into) == 2):
+                raise ValueError('ClsStager: into is an (x, target) pair of device tensors')
+            into = {'images': into[0], 'target': into[1]}
+        return self._queue('ClsStager', batch, forms, specs, into, after)
+
+    def _table(self, shape, hold):
+        """this batch's erase table on the device (drawn now, once the batch has been accepted), or None.  The host copy is pinned
+        anew for every batch -- 35 KB at B = 128, served from torch's pinned-memory cache after the first -- and held until the
+        batch's event has completed."""
+        if self.random_erasing is None:
+            return None
+        host = torch.from_numpy(self.random_erasing.draw(tuple(shape))).pin_memory()
+        hold.append(host)
+        return host.to(self.device, non_blocking=True)
+
+    def _stage_one(self, task, h, form, o, hold):
+        if task == 'target' or form == 'reference':
+            d = torch.empty(h.shape, dtype=h.dtype, device=self.device) if o is None else o
+            d.copy_(h, non_blocking=True)
+            if task == 'images' and self.random_erasing is not None and self.erase_float32:
+                data_ops.random_erase_(d, self._table(h.shape, hold))
+            return d
+        d = torch.empty(h.shape, dtype=h.dtype, device=self.device)
+        d.copy_(h, non_blocking=True)
+        return data_ops.ingest_rgb_u8_chw(d, self.table, self._table(h.shape, hold), out=o)
+
+    def get(self, staged: StagedBatch):
+        """``(x, target)`` on the device, safe to use on the current stream (``BatchStager.get``)."""
+        t = super().get(staged)
+        return t['images'], t['target']
+
+
+class ClsStagedLoader(StagedLoader):
+    """``StagedLoader`` over a classification DataLoader's ``(images, target)`` batches: yields ``(x_on_device, target_on_device)``,
+    batch k + 1 staged (copied, normalised, erased) under step k."""
+
+    def __init__(self, iterable, stager: ClsStager):
+        if not isinstance(stager, ClsStager):
+            raise ValueError(f'ClsStagedLoader: the stager must be a ClsStager, got {type(stager).__name__}')
+        super().__init__(iterable, stager)
+
+    def _stage(self, item):
+        return self.stager.stage(item)
+
+    def _get(self, staged):
+        return self.stager.get(staged)
