@@ -88,6 +88,13 @@ const char* mmae_last_error(void);
  *         -- the same pair with the derivative evaluated once, in the forward epilogue that has the erf terms in registers
  *            anyway, so that the backward epilogue is a multiply (Mlp.forward / its backward, multimae_utils.py:137-149;
  *            the composite encoder / decoder calls use this pair for bf16 activations).  Same kernels and restrictions.
+ *   epi = MMAE_EPI_GELU_Y: v = gelu_erf(v), ONE output stream: aux is ignored (may be NULL) and nothing is written beside C.  For a
+ *         forward that no backward follows (mmae_stack_fwd_infer).  C holds the bits the two-stream
+ *         epilogues leave there: same kernel and tile for the same problem, same GELU routine -- chosen, as theirs, by c_dtype and
+ *         aux_dtype, so set aux_dtype and ldaux as the two-stream call would.  It exists as a compiled flavour of the ping-pong kernel
+ *         only: bf16 operands and C, bias, k-contiguous operands, K % 32 == 0, 8-aligned widths, a shape mmae_gemm_plan gives tile 9 / 10
+ *         (M >= 2 048, N >= 192, K >= 128).  Any other product: MMAE_ESUPPORT before anything is launched -- no other kernel's epilogue
+ *         was touched for it (dropping GELU' from the exact-erf form moves the last bit of GELU: the compiler contracts differently).
  * bf16 operands need lda/ldb % 8 == 0 and 16-byte aligned bases; a k-contiguous
  * operand may have any K as long as the bytes up to the next multiple of 8 along
  * k are readable and finite, and zero in at least one of the two operands: both
@@ -99,6 +106,7 @@ const char* mmae_last_error(void);
 #define MMAE_EPI_DGELU 2
 #define MMAE_EPI_GELU_G 3
 #define MMAE_EPI_MUL   4
+#define MMAE_EPI_GELU_Y 5
 
 typedef struct mmae_gemm_desc {
     const void* A; const void* B; void* C;
@@ -155,7 +163,8 @@ typedef struct mmae_gemm_desc {
        ln_out[M][N] in the operands' 16-bit format: LayerNorm(C) with ln_gamma / ln_beta / ln_eps and the row statistics into ln_mean /
        ln_rstd [M] -- the nn.LayerNorm that follows the Linear (multimae_utils.py:229-232, output_adapters.py:265-266) without its own
        pass -- or, with ln_gamma == NULL, the plain 16-bit cast of C (the autocast cast in front of the next Linear).  ln_out == NULL = off.
-       MMAE_ESUPPORT for any other product. */
+       ln_mean == ln_rstd == NULL with ln_gamma set (bf16 only): the same LayerNorm without the statistics stores, ln_out bit-equal -- the
+       forward of a pass no backward follows (mmae_stack_fwd_infer).  MMAE_ESUPPORT for any other product. */
     const float* ln_gamma; const float* ln_beta; void* ln_out; float* ln_mean; float* ln_rstd; float ln_eps;
 } mmae_gemm_desc;
 
@@ -305,6 +314,10 @@ int mmae_gemm_dw_group(const mmae_dw_group_desc* d, void* stream);
  * ------------------------------------------------------------------------- */
 int mmae_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int y_dtype,
                        float* mean, float* rstd, int64_t R, int D, float eps, void* stream);
+/* The forward for a pass that no backward follows: the same row arithmetic (an instantiation of the same routine chosen at compile
+ * time), y bit-equal to mmae_layernorm_fwd's, mean / rstd neither taken nor written.  y_dtype MMAE_BF16 or MMAE_F32. */
+int mmae_layernorm_fwd_nostat(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, int64_t R, int D, float eps,
+                              void* stream);
 int mmae_layernorm_bwd_nblk(int64_t R);
 int mmae_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float* gamma,
                        const float* mean, const float* rstd, const float* dx_in, float* dx_out,
@@ -425,6 +438,15 @@ int mmae_attn_bwd_tiled(const void* q, const void* k, const void* v, const void*
                         void* dk, void* dv, int B, int H, int Nq, int Nk, int hd, int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr,
                         int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr, int64_t dq_sb, int64_t dq_sr, int64_t dk_sb, int64_t dk_sr,
                         int64_t dv_sb, int64_t dv_sr, float scale, void* stream);
+/* The attention forwards of a pass that no backward follows: lse is neither taken nor written.  Each launches the no-lse instantiation
+ * (a template parameter, not a pointer test) of the kernel its twin launches for the same geometry, so o is bit-equal to the twin's.
+ * mode: 0 = mmae_attn_fwd (bf16), 1 = mmae_attn_fwd_f32x3, 2 = mmae_attn_fwd_f32f16; operands, strides and limits as theirs. */
+int mmae_attn_fwd_nolse(int mode, const void* q, const void* k, const void* v, void* o, int B, int H, int Nq, int Nk, int hd,
+                        int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
+                        float scale, void* stream);
+int mmae_attn_fwd_tiled_nolse(const void* q, const void* k, const void* v, void* o, int B, int H, int Nq, int Nk, int hd,
+                              int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
+                              float scale, void* stream);
 
 
 /* ------------------------------------------------------------------------- *
@@ -540,6 +562,23 @@ int64_t mmae_stack_tmp_bytes(const mmae_stack_desc* d);
 int64_t mmae_stack_out_offset(const mmae_stack_desc* d, int l);
 int mmae_stack_fwd(const mmae_stack_desc* d, void* stream);
 int mmae_stack_bwd(const mmae_stack_desc* d, void* stream, void* side_stream);
+/* The stack's forward when no backward follows (evaluation under no-grad, EMA evaluation, feature extraction): mmae_stack_fwd's launch
+ * sequence with the side outputs of the backward compiled out -- fc1 stores GELU alone where its product has the one-stream flavour
+ * (MMAE_EPI_GELU_Y: the ping-pong GEMM, bf16 at >= 2 048 rows: every evaluation geometry; any other fc1 keeps mmae_block_fwd's epilogue
+ * and its second stream lands in scratch that is dead by then), the LayerNorms keep no mean / rstd (mmae_layernorm_fwd_nostat; at D = 256 the side output of the proj product without its
+ * statistics), the attention keeps no lse (mmae_attn_fwd_nolse / _tiled_nolse).  Every stored value comes from the same kernel, tile
+ * and instruction sequence as in mmae_stack_fwd: the outputs of the two calls are equal bit for bit.  No atomics.
+ *   outs  host array [L] of device f32 [R][D] destinations or NULL: block l's output goes to outs[l] when given (return_all_layers,
+ *         the DPT hooks), otherwise into one of two buffers of the scratch that the unkept layers take in turn.  outs[L-1] is required.
+ *   act / act_bytes  scratch of mmae_stack_infer_bytes() bytes: ONE block's ln1, qkv, ao, ln2, hact, x1 and the two rotating outputs
+ *         (the second stream of a two-stream fc1 aliases ln1 | qkv | ao; only Hd > 5 D adds bytes for it).
+ *         Its size does not depend on L (a ViT-B stack at 37 824 rows: 0.9 GB against mmae_stack_act_bytes' 12.6 GB); nothing in it
+ *         means anything after the call.
+ *   g, d_out, dx, tmp, l_begin, l_end, grad_acc are ignored.
+ * bf16 activations, or f32 with MMAE_F32X3 / MMAE_F32F16 products; geometry limits as mmae_stack_fwd.  mx_w != NULL or any non-NULL dp
+ * entry: MMAE_ESUPPORT (the caller keeps mmae_stack_fwd for those). */
+int64_t mmae_stack_infer_bytes(const mmae_stack_desc* d);
+int mmae_stack_fwd_infer(const mmae_stack_desc* d, float* const* outs, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * SpatialOutputAdapter.forward (output_adapters.py:236-282) and its autograd as ONE call per direction: proj_context,

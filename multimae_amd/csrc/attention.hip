@@ -279,7 +279,8 @@ template <> struct ActOf<true> { typedef float T; };
 // -------------------------------------------------------------------------------------------------
 // GRP (with NT = 4): more than 128 keys are walked in groups of four key tiles with the running (max, sum) rescale of flash attention -- 64
 // score registers instead of 112 / 128, so three waves per SIMD fit where the single-group form of the 196-key decoder grids (NT = 7) holds two.
-template <int HD, int NT, int MODE, bool GRP = false>
+// LSE = false: the same kernel without the lse store -- the forward of a pass that no backward follows (mmae_attn_fwd_nolse)
+template <int HD, int NT, int MODE, bool GRP = false, bool LSE = true>
 __global__ void __launch_bounds__(256, (NT == 4 && MODE != 1) ? 3 : (NT <= 7 ? 2 : 1)) attn_fwd_kernel(const AttnArgs a) {
     static_assert(!GRP || NT == 4, "grouped form: four key tiles per group");
     constexpr bool X3 = MODE == 1, F32IO = MODE == 1 || MODE == 2;      // MODE 3: fp16 tensors in memory (MMAE_F16)
@@ -398,7 +399,9 @@ __global__ void __launch_bounds__(256, (NT == 4 && MODE != 1) ? 3 : (NT <= 7 ? 2
 #pragma unroll
                 for (int dt = 0; dt < HD / 32; ++dt) store_row32_mx(a, (long long)b * a.Nq + q, a.mx_col[0] + h * HD + dt * 32, o[dt], inv, hi, qok);
             }
-            if (qok && hi == 0) a.lse[((long long)b * a.H + h) * a.Nq + q] = m * 0.69314718056f + __logf(l);     // natural-log lse, as before
+            if constexpr (LSE) {
+                if (qok && hi == 0) a.lse[((long long)b * a.H + h) * a.Nq + q] = m * 0.69314718056f + __logf(l);     // natural-log lse, as before
+            }
         }
     }
 }
@@ -885,7 +888,7 @@ struct TiledArgs {
 };
 constexpr int TROWS = 128;                                  // rows per LDS tile and per workgroup
 
-template <int HD>
+template <int HD, bool LSE = true>                          // LSE = false: without the lse store (mmae_attn_fwd_tiled_nolse)
 __global__ void __launch_bounds__(256, 2) attn_fwd_tiled_kernel(const TiledArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int tile_b = TROWS * HD * 2;                  // smem: [K0 | V0 | K1 | V1]
@@ -990,7 +993,9 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_tiled_kernel(const TiledArgs 
         uint16_t* ob = a.out + b * a.o_sb + h * HD + (long long)q * a.o_sr;
 #pragma unroll
         for (int dt = 0; dt < HD / 32; ++dt) store_row32<false>(ob + dt * 32, o[dt], inv, hi, qok);
-        if (qok && hi == 0) a.lse[((long long)b * a.H + h) * a.Nq + q] = m * 0.69314718056f + __logf(l);
+        if constexpr (LSE) {
+            if (qok && hi == 0) a.lse[((long long)b * a.H + h) * a.Nq + q] = m * 0.69314718056f + __logf(l);
+        }
     }
 }
 
@@ -1263,6 +1268,19 @@ int launch_fwd(const AttnArgs& a, size_t lds, hipStream_t st) {
     if (a.nkp <= 224) return mmae_launch_lds<attn_fwd_kernel<HD, 7, MODE>>(grid, block, lds, st, what, a);
     return mmae_launch_lds<attn_fwd_kernel<HD, 8, MODE>>(grid, block, lds, st, what, a);
 }
+// the no-lse instantiations, chosen by the same conditions (the outputs must be launch_fwd's bit for bit)
+template <int HD, int MODE>
+int launch_fwd_nolse(const AttnArgs& a, size_t lds, hipStream_t st) {
+    const dim3 grid(a.B * a.H), block(256);
+    const char* what = "attn_fwd_nolse";
+    if (a.nkp <= 128) return mmae_launch_lds<attn_fwd_kernel<HD, 4, MODE, false, false>>(grid, block, lds, st, what, a);
+    if constexpr (HD == 32 && (MODE == 0 || MODE == 3)) {
+        static const int env_grp = mmae_env_int("MMAE_ATTN_FWD_GRP", 1);
+        if (env_grp) return mmae_launch_lds<attn_fwd_kernel<HD, 4, MODE, true, false>>(grid, block, lds, st, what, a);
+    }
+    if (a.nkp <= 224) return mmae_launch_lds<attn_fwd_kernel<HD, 7, MODE, false, false>>(grid, block, lds, st, what, a);
+    return mmae_launch_lds<attn_fwd_kernel<HD, 8, MODE, false, false>>(grid, block, lds, st, what, a);
+}
 
 template <int HD, int MODE>
 int launch_bwd(const AttnArgs& a, size_t lds, hipStream_t st) {
@@ -1289,9 +1307,9 @@ extern "C" {
 
 static int attn_fwd_impl(int mode, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int hd,
                          int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
-                         float scale, void* stream, void* mx_q = nullptr, void* mx_scale = nullptr) {
+                         float scale, void* stream, void* mx_q = nullptr, void* mx_scale = nullptr, bool want_lse = true) {
     const bool x3 = mode == 1;                            // mode: 0 bf16, 1 f32 activations / split-bf16 products, 2 f32 activations / fp16 products, 3 fp16 activations
-    MMAE_REQUIRE(q && k && v && o && lse, "attn_fwd: null pointer");
+    MMAE_REQUIRE(q && k && v && o && (lse || !want_lse), "attn_fwd: null pointer");
     const long long st[] = {q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr};
     const int rc = check_common(B, H, Nq, Nk, hd, st, 8);
     MMAE_REQUIRE(rc == 0, rc == -2 ? "attn: head_dim must be 32 or 64" : (rc == -3 ? "attn: strides must be multiples of 8" : "attn: need 1 <= Nq, Nk <= 256"));
@@ -1305,6 +1323,14 @@ static int attn_fwd_impl(int mode, const void* q, const void* k, const void* v, 
         a.mx_q = (unsigned char*)mx_q; a.mx_s = (unsigned char*)mx_scale; a.mx_rows = (long long)B * Nq; a.mx_ld = H * hd;
     }
     const size_t lds = (size_t)2 * a.nkp * hd * 2 * (x3 ? 2 : 1);
+    if (!want_lse) {                                      // modes 0 - 2: what mmae_stack_fwd_infer runs
+        MMAE_REQUIRE(mode != 3 && !mx_q, "attn_fwd_nolse: bf16 or f32 activations");
+        switch (mode) {
+            case 1: return hd == 64 ? launch_fwd_nolse<64, 1>(a, lds, (hipStream_t)stream) : launch_fwd_nolse<32, 1>(a, lds, (hipStream_t)stream);
+            case 2: return hd == 64 ? launch_fwd_nolse<64, 2>(a, lds, (hipStream_t)stream) : launch_fwd_nolse<32, 2>(a, lds, (hipStream_t)stream);
+            default: return hd == 64 ? launch_fwd_nolse<64, 0>(a, lds, (hipStream_t)stream) : launch_fwd_nolse<32, 0>(a, lds, (hipStream_t)stream);
+        }
+    }
     return by_hd_mode(hd, mode, [&](auto HD, auto MODE) { return launch_fwd<decltype(HD)::value, decltype(MODE)::value>(a, lds, (hipStream_t)stream); });
 }
 
@@ -1357,6 +1383,13 @@ int mmae_attn_fwd(const void* q, const void* k, const void* v, void* o, float* l
                   int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
                   float scale, void* stream) {
     return attn_fwd_impl(0, q, k, v, o, lse, B, H, Nq, Nk, hd, q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr, scale, stream);
+}
+/* mmae_attn_fwd / _f32x3 / _f32f16 (mode 0 / 1 / 2) without the lse output: the same kernels' no-lse instantiations, o bit-equal */
+int mmae_attn_fwd_nolse(int mode, const void* q, const void* k, const void* v, void* o, int B, int H, int Nq, int Nk, int hd,
+                        int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
+                        float scale, void* stream) {
+    MMAE_REQUIRE(mode >= 0 && mode <= 2, "attn_fwd_nolse: mode 0 (bf16), 1 (f32, split-bf16 products) or 2 (f32, fp16 products)");
+    return attn_fwd_impl(mode, q, k, v, o, nullptr, B, H, Nq, Nk, hd, q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr, scale, stream, nullptr, nullptr, false);
 }
 int mmae_attn_fwd_mx(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int hd,
                      int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
@@ -1423,10 +1456,10 @@ int mmae_attn_bwd_f16(const void* q, const void* k, const void* v, const void* o
 }
 
 /* Tiled bf16 attention, any sequence length (see the kernels' header comment).  Same operands and lse as mmae_attn_fwd. */
-int mmae_attn_fwd_tiled(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int hd,
-                        int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
-                        float scale, void* stream) {
-    MMAE_REQUIRE(q && k && v && o && lse, "attn_fwd_tiled: null pointer");
+static int attn_fwd_tiled_impl(const void* q, const void* k, const void* v, void* o, float* lse, bool want_lse, int B, int H, int Nq, int Nk, int hd,
+                               int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
+                               float scale, void* stream) {
+    MMAE_REQUIRE(q && k && v && o && (lse || !want_lse), "attn_fwd_tiled: null pointer");
     const long long st[] = {q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr};
     const int rc = check_tiled(B, H, Nq, Nk, hd, st, 8);
     MMAE_REQUIRE(rc == 0, tiled_msg(rc));
@@ -1438,7 +1471,21 @@ int mmae_attn_fwd_tiled(const void* q, const void* k, const void* v, void* o, fl
     const dim3 grid((unsigned)(B * H * ((Nq + TROWS - 1) / TROWS))), block(256);
     hipStream_t s = (hipStream_t)stream;
     const char* what = "attn_fwd_tiled";
+    if (!want_lse)
+        return hd == 64 ? mmae_launch_lds<attn_fwd_tiled_kernel<64, false>>(grid, block, lds, s, what, a)
+                        : mmae_launch_lds<attn_fwd_tiled_kernel<32, false>>(grid, block, lds, s, what, a);
     return hd == 64 ? mmae_launch_lds<attn_fwd_tiled_kernel<64>>(grid, block, lds, s, what, a) : mmae_launch_lds<attn_fwd_tiled_kernel<32>>(grid, block, lds, s, what, a);
+}
+int mmae_attn_fwd_tiled(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int hd,
+                        int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
+                        float scale, void* stream) {
+    return attn_fwd_tiled_impl(q, k, v, o, lse, true, B, H, Nq, Nk, hd, q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr, scale, stream);
+}
+/* mmae_attn_fwd_tiled without the lse output (the no-lse instantiation of the same kernel, o bit-equal) */
+int mmae_attn_fwd_tiled_nolse(const void* q, const void* k, const void* v, void* o, int B, int H, int Nq, int Nk, int hd,
+                              int64_t q_sb, int64_t q_sr, int64_t k_sb, int64_t k_sr, int64_t v_sb, int64_t v_sr, int64_t o_sb, int64_t o_sr,
+                              float scale, void* stream) {
+    return attn_fwd_tiled_impl(q, k, v, o, nullptr, false, B, H, Nq, Nk, hd, q_sb, q_sr, k_sb, k_sr, v_sb, v_sr, o_sb, o_sr, scale, stream);
 }
 
 /* Backward of mmae_attn_fwd_tiled: two launches (dq, which also writes delta; then dk / dv, which reads it).  o is accepted for symmetry with

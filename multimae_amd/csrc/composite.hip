@@ -434,6 +434,26 @@ BlockAct carve_block_act(Carver& cv, int B, int N, int D, int heads, int Hd, siz
     return a;
 }
 
+// scratch of mmae_stack_fwd_infer: ONE block's activations (no GELU' / pre-activation, no LayerNorm statistics, no lse) and two block
+// outputs that the layers without a destination of their own take in turn -- nothing per layer
+struct InferAct {
+    void *ln1, *qkv, *ao, *ln2, *hact, *haux;             // haux: where fc1's second stream goes when the product has no one-stream flavour:
+                                                          // it ALIASES ln1 | qkv | ao, which are dead by the time fc1 runs (same stream)
+    float *x1, *rot[2];
+};
+InferAct carve_infer_act(Carver& cv, int B, int N, int D, int Hd, size_t es) {
+    const int64_t R = (int64_t)B * N;
+    InferAct a;
+    auto pad = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t o_qkv = pad(R * D * es), o_ao = o_qkv + pad(R * 3 * D * es), three = o_ao + pad(R * D * es);
+    char* u = (char*)cv.take(three > R * Hd * es ? three : R * Hd * es);
+    a.ln1 = u; a.qkv = u + o_qkv; a.ao = u + o_ao; a.haux = u;
+    a.ln2 = cv.take(R * D * es);
+    a.hact = cv.take(R * Hd * es);
+    a.x1 = cv.takeT<float>(R * D); a.rot[0] = cv.takeT<float>(R * D); a.rot[1] = cv.takeT<float>(R * D);
+    return a;
+}
+
 struct BlockTmp {       // backward temporaries of one block
     void *d_hpre, *d_ln2, *d_ao, *d_qkv, *d_ln1, *dx1_act, *dx0_act, *dxs_act;
     float *dx1, *dx0, *part_h, *part1, *part2;
@@ -829,6 +849,73 @@ int mmae_stack_fwd(const mmae_stack_desc* d, void* stream) {
         if (d->mx_w) { b.mx_w = d->mx_w + 16 * l; b.mx_tmp = mx_tmp; b.mx_tmp_bytes = stack_mx_tmp_bytes(d); }
         if ((rc = mmae_block_fwd(&b, st))) return rc;
         x = acts[l].x2;
+    }
+    return 0;
+}
+
+// ---- the forward that no backward follows ----------------------------------------------------------------------------------
+// block_fwd_impl's launch sequence for a block without stochastic depth or MX products, every launch in its one-output form: the
+// LayerNorms without their statistics, the attention without its lse, fc1 with the one-stream GELU epilogue (MMAE_EPI_GELU_Y).  Each is
+// the SAME kernel for the same problem with the side store compiled out, so what is stored has mmae_block_fwd's bits.
+static int block_fwd_infer(const mmae_block_desc* d, hipStream_t st) {
+    const Ctx c = ctx_of(d);
+    const int R = d->B * d->N, D = d->D, Hd = d->Hd, N = d->N, act = d->act_dtype, hd = D / d->heads;
+    int rc;
+    if ((rc = mmae_layernorm_fwd_nostat(d->x0, d->n1_w, d->n1_b, d->ln1, act, R, D, d->eps, st))) return rc;
+    if ((rc = lin_fwd(c, d->ln1, d->qkv_w, d->qkv_b, d->qkv, act, R, 3 * D, D, nullptr, nullptr, MMAE_EPI_NONE, st))) return rc;
+    {
+        const size_t es = es_of(act);
+        const char* qkv = (const char*)d->qkv;
+        const float scale = 1.0f / sqrtf((float)hd);
+        const int64_t sb = (int64_t)N * 3 * D;
+        if (act == MMAE_BF16 && N > 256)
+            rc = mmae_attn_fwd_tiled_nolse(qkv, qkv + (size_t)D * es, qkv + (size_t)2 * D * es, d->ao, d->B, d->heads, N, N, hd, sb, 3 * D, sb, 3 * D, sb, 3 * D,
+                                           (int64_t)N * D, D, scale, st);
+        else
+            rc = mmae_attn_fwd_nolse(act == MMAE_BF16 ? 0 : (d->f32_gemm == MMAE_F32F16 ? 2 : 1), qkv, qkv + (size_t)D * es, qkv + (size_t)2 * D * es, d->ao,
+                                     d->B, d->heads, N, N, hd, sb, 3 * D, sb, 3 * D, sb, 3 * D, (int64_t)N * D, D, scale, st);
+        if (rc) return rc;
+    }
+    const bool side = ln_side_ok(c, D, D, MMAE_F32) && (Hd % 32) == 0;     // block_fwd_impl's condition: norm2 rides on the proj product at D = 256
+    const LnSide ln2s = {d->n2_w, d->n2_b, d->ln2, nullptr, nullptr, d->eps};
+    if ((rc = lin_fwd(c, d->ao, d->proj_w, d->proj_b, d->x1, MMAE_F32, R, D, D, d->x0, nullptr, MMAE_EPI_NONE, st, nullptr, -1, -1, side ? &ln2s : nullptr))) return rc;
+    if (!side && (rc = mmae_layernorm_fwd_nostat(d->x1, d->n2_w, d->n2_b, d->ln2, act, R, D, d->eps, st))) return rc;
+    // fc1: the one-stream GELU flavour where the product has one (the ping-pong kernel: bf16, >= 2 048 rows -- every evaluation geometry);
+    // elsewhere mmae_block_fwd's own epilogue, its second stream going to scratch that nothing reads.  Refused before anything is launched.
+    rc = lin_fwd(c, d->ln2, d->fc1_w, d->fc1_b, d->hact, act, R, Hd, D, nullptr, nullptr, MMAE_EPI_GELU_Y, st);
+    if (rc == MMAE_ESUPPORT) rc = lin_fwd(c, d->ln2, d->fc1_w, d->fc1_b, d->hact, act, R, Hd, D, nullptr, d->hpre, epi_gelu(act), st);
+    if (rc) return rc;
+    return lin_fwd(c, d->hact, d->fc2_w, d->fc2_b, d->x2, MMAE_F32, R, D, Hd, d->x1, nullptr, MMAE_EPI_NONE, st);
+}
+
+int64_t mmae_stack_infer_bytes(const mmae_stack_desc* d) {
+    if (!d || d->L <= 0) return 0;
+    Carver cv(nullptr);
+    (void)carve_infer_act(cv, d->B, d->N, d->D, d->Hd, d->act_dtype == MMAE_BF16 ? 2 : 4);
+    return cv.off;
+}
+
+int mmae_stack_fwd_infer(const mmae_stack_desc* d, float* const* outs, void* stream) {
+    MMAE_REQUIRE(d, "stack_fwd_infer: null descriptor");
+    if (d->mx_w) { mmae_set_error("stack_fwd_infer: MX-fp8 products are outside the inference forward (mmae_stack_fwd runs them)"); return MMAE_ESUPPORT; }
+    if (stack_has_dp(d)) { mmae_set_error("stack_fwd_infer: stochastic-depth scales are outside the inference forward (mmae_stack_fwd runs them)"); return MMAE_ESUPPORT; }
+    int rc = check_stack(d);
+    if (rc) return rc;
+    MMAE_REQUIRE(d->L <= 64, "stack: at most 64 blocks");
+    MMAE_REQUIRE(outs && outs[d->L - 1], "stack_fwd_infer: the destination of the last block's output is required");
+    MMAE_REQUIRE(d->act_bytes >= mmae_stack_infer_bytes(d), "stack_fwd_infer: scratch slab too small (mmae_stack_infer_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    Carver cv(d->act);
+    const InferAct a = carve_infer_act(cv, d->B, d->N, d->D, d->Hd, d->act_dtype == MMAE_BF16 ? 2 : 4);
+    const float* x = d->x;
+    for (int l = 0; l < d->L; ++l) {
+        mmae_block_desc b = {};
+        fill_block_params(b, d->B, d->N, d->D, d->heads, d->Hd, d->act_dtype, d->f32_gemm, d->eps, d->w + 4 * l, d->p + 8 * l);
+        b.x0 = x; b.ln1 = a.ln1; b.qkv = a.qkv; b.ao = a.ao; b.x1 = a.x1; b.ln2 = a.ln2; b.hact = a.hact; b.hpre = a.haux;
+        b.x2 = outs[l] ? outs[l] : a.rot[l & 1];          // block l reads what block l - 1 wrote: never the buffer it writes
+        b.ws_main = d->ws_main; b.ws_main_elems = d->ws_main_elems;
+        if ((rc = block_fwd_infer(&b, st))) return rc;
+        x = b.x2;
     }
     return 0;
 }

@@ -81,6 +81,7 @@ int mmae_gemm_bf16_pp_impl(const mmae_gemm_desc* d, const GemmArgs& g, int code,
         }
     }
     if (g.ln_out) { mmae_set_error("gemm: no instantiation with the LayerNorm side output for this product"); return MMAE_ESUPPORT; }
+    if (g.aux_grad == 2) { mmae_set_error("gemm: MMAE_EPI_GELU_Y has no instantiation outside the flavoured ping-pong kernels"); return MMAE_ESUPPORT; }
     if (code == 10 && !aks) {
         return bks ? launch<5, false, true>(g, d->batch, st) : launch<5, false, false>(g, d->batch, st);
     }

@@ -1,6 +1,6 @@
 // bf16 MFMA ping-pong GEMM: instantiations with the epilogue flavour fixed at compile time (gemm_common.h, gemm_flavour()).
-// Only the flavours the MultiMAE step actually launches: forward Linear layers (bias -> bf16 / bias + GELU -> bf16 x 2 / bias
-// [+ residual] -> f32) and their dX products (bf16, bf16 x dGELU [+ column sums], f32).  Anything else returns MMAE_ESUPPORT
+// Only the flavours the MultiMAE step actually launches: forward Linear layers (bias -> bf16 / bias + GELU -> bf16 x 2, or x 1 for
+// the inference forward / bias [+ residual] -> f32) and their dX products (bf16, bf16 x dGELU [+ column sums], f32).  Anything else returns MMAE_ESUPPORT
 // and the caller launches the generic kernel.
 #include "gemm_pp_body.h"
 
@@ -20,8 +20,14 @@ int mmae_gemm_bf16_pp_fl_impl(const mmae_gemm_desc* d, const GemmArgs& g, int co
     if (g.ln_out) {                               // LayerNorm / cast side output: the f32 flavours of the 256 x 256 tile, N == 256 (runtime.hip checks)
         if (bks || t10 || g.N != 256) return MMAE_ESUPPORT;
         if (g.h16) {
+            if (g.ln_g && !g.ln_mean) return MMAE_ESUPPORT;
             if (fl == FL_F32_BIAS_RESID) return launch<4, false, false, FL_F32_BIAS_RESID, KFV, true, true>(g, d->batch, st);
             if (fl == FL_F32_BIAS) return launch<4, false, false, FL_F32_BIAS, KFV, true, true>(g, d->batch, st);
+            return MMAE_ESUPPORT;
+        }
+        if (g.ln_g && !g.ln_mean) {               // LayerNorm side output without its statistics (a forward no backward follows; runtime.hip: both NULL)
+            if (fl == FL_F32_BIAS_RESID) return launch<4, false, false, FL_F32_BIAS_RESID, KFV, false, true, false>(g, d->batch, st);
+            if (fl == FL_F32_BIAS) return launch<4, false, false, FL_F32_BIAS, KFV, false, true, false>(g, d->batch, st);
             return MMAE_ESUPPORT;
         }
         if (fl == FL_F32_BIAS_RESID) return launch<4, false, false, FL_F32_BIAS_RESID, KFV, false, true>(g, d->batch, st);
@@ -52,6 +58,7 @@ int mmae_gemm_bf16_pp_fl_impl(const mmae_gemm_desc* d, const GemmArgs& g, int co
             switch (fl) {
                 case FL_BF16_BIAS: return launch<5, false, false, FL_BF16_BIAS, KFV>(g, d->batch, st);
                 case FL_BF16_BIAS_GELU: return launch<5, false, false, FL_BF16_BIAS_GELU, KFV>(g, d->batch, st);
+                case FL_BF16_BIAS_GELU_Y: return launch<5, false, false, FL_BF16_BIAS_GELU_Y, KFV>(g, d->batch, st);
                 case FL_F32_BIAS_RESID: return launch<5, false, false, FL_F32_BIAS_RESID, KFV>(g, d->batch, st);
                 case FL_F32_BIAS: return launch<5, false, false, FL_F32_BIAS, KFV>(g, d->batch, st);
                 default: return MMAE_ESUPPORT;
@@ -60,6 +67,7 @@ int mmae_gemm_bf16_pp_fl_impl(const mmae_gemm_desc* d, const GemmArgs& g, int co
         switch (fl) {
             case FL_BF16_BIAS: return launch<4, false, false, FL_BF16_BIAS, KFV>(g, d->batch, st);
             case FL_BF16_BIAS_GELU: return launch<4, false, false, FL_BF16_BIAS_GELU, KFV>(g, d->batch, st);
+            case FL_BF16_BIAS_GELU_Y: return launch<4, false, false, FL_BF16_BIAS_GELU_Y, KFV>(g, d->batch, st);
             case FL_F32_BIAS_RESID: return launch<4, false, false, FL_F32_BIAS_RESID, KFV>(g, d->batch, st);
             case FL_F32_BIAS: return launch<4, false, false, FL_F32_BIAS, KFV>(g, d->batch, st);
             default: return MMAE_ESUPPORT;

@@ -20,7 +20,9 @@ struct GemmArgs {
     float* acs;                   // optional [splitk][M] partial column sums of the k-strided A operand (ping-pong kernel)
     float* colpart;               // optional [ceil(M/32)][N] column sums of the epilogue output per 32-row block (dGELU flavour)
     int wide_st;                  // bf16 epilogues with 8-column (16-byte) lanes (store_tile64_bf16x8); env MMAE_EPI_WIDE=0 turns it off
-    int aux_grad;                 // MMAE_EPI_GELU_G / MMAE_EPI_MUL: aux keeps GELU'(pre-activation) instead of the pre-activation (mmae.h)
+    int aux_grad;                 // MMAE_EPI_GELU_G / MMAE_EPI_MUL: aux keeps GELU'(pre-activation) instead of the pre-activation (mmae.h);
+                                  // 2 = MMAE_EPI_GELU_Y: GELU with ONE output stream, aux not written (NULL) -- a flavour of the ping-pong kernel
+                                  // only (FL_BF16_BIAS_GELU_Y); runtime.hip refuses every product that would reach another store routine
     int dephase;                  // experiment (env MMAE_PP_DEPHASE = n + 256 * mode): some workgroups of the ping-pong kernel start n x ~4 us late
     const void* scA; const void* scB;   // MX-fp8 products: packed E8M0 scales of the two operands (mxfp8.hip)
     unsigned char* qout; unsigned char* qsc; long long ldq;   // ..._Q flavours: also emit the MX-fp8 quantisation of the bf16 output C ([M][ldq] bytes + packed scales)
@@ -534,7 +536,8 @@ __device__ __forceinline__ void gemm_store_tile64(const GemmArgs& g, char* Cz, c
 // ------------------------------------------------------------------------------------------------
 enum { FL_GENERIC = 0, FL_BF16_BIAS = 1, FL_F32_BIAS_RESID = 2, FL_BF16_BIAS_GELU = 3, FL_BF16 = 4, FL_BF16_DGELU_CS = 5, FL_F32_BIAS = 6, FL_F32 = 7,
        FL_BF16_DGELU = 8,
-       FL_BF16_BIAS_GELU_Q = 9, FL_BF16_DGELU_CS_Q = 10, FL_BF16_DGELU_Q = 11 };      // + MX-fp8 copy of the output (mxfp8.hip only)
+       FL_BF16_BIAS_GELU_Q = 9, FL_BF16_DGELU_CS_Q = 10, FL_BF16_DGELU_Q = 11,        // + MX-fp8 copy of the output (mxfp8.hip only)
+       FL_BF16_BIAS_GELU_Y = 12 };                                                     // bias + GELU -> ONE bf16 stream (MMAE_EPI_GELU_Y: the inference forward's fc1)
 
 static inline int gemm_flavour(const GemmArgs& g, int batch) {
     if (batch != 1 || g.splitk > 1 || !g.vec || (g.N & 3) || g.alpha != 1.0f || g.accumulate || g.dbg) return FL_GENERIC;
@@ -553,7 +556,7 @@ static inline int gemm_flavour(const GemmArgs& g, int batch) {
                       (!bias || ((uintptr_t)g.bias & 15) == 0);
     if (!wide) return FL_GENERIC;
     if (g.epi == MMAE_EPI_NONE) return bias ? FL_BF16_BIAS : FL_BF16;
-    if (g.epi == MMAE_EPI_GELU && bias) return FL_BF16_BIAS_GELU;
+    if (g.epi == MMAE_EPI_GELU && bias) return g.aux_grad == 2 ? FL_BF16_BIAS_GELU_Y : FL_BF16_BIAS_GELU;
     if (g.epi == MMAE_EPI_DGELU && !bias) return g.colpart ? FL_BF16_DGELU_CS : FL_BF16_DGELU;
     return FL_GENERIC;
 }
@@ -567,6 +570,8 @@ __device__ __forceinline__ void gemm_store_tile64_fl(const GemmArgs& g, char* Cz
 #define MMAE_AUXG(...) do { if (g.aux_grad) store_tile64_bf16x8<__VA_ARGS__, 1>(g, Cz, wave_lds, lane, acc, m_base, n_base, ntm); \
                             else store_tile64_bf16x8<__VA_ARGS__, 0>(g, Cz, wave_lds, lane, acc, m_base, n_base, ntm); } while (0)
     else if (FL == FL_BF16_BIAS_GELU) MMAE_AUXG(true, MMAE_EPI_GELU, false, 0, 4, false, H16);
+    // the same routine without its aux store (the DBG = 2 form: GELU arithmetic kept, pre-activation / GELU' stream dropped)
+    else if (FL == FL_BF16_BIAS_GELU_Y) store_tile64_bf16x8<true, MMAE_EPI_GELU, false, 2, 4, false, H16, 0>(g, Cz, wave_lds, lane, acc, m_base, n_base, ntm);
     // (with one flavour per instantiation there are registers to spare: all 8 pre-activation loads of a 64-row tile go out before its first use)
     else if (FL == FL_BF16_DGELU_CS) MMAE_AUXG(false, MMAE_EPI_DGELU, true, 0, 4, false, H16);
     else if (FL == FL_BF16_DGELU) MMAE_AUXG(false, MMAE_EPI_DGELU, false, 0, 8, false, H16);

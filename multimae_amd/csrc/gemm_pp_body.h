@@ -126,7 +126,9 @@ __device__ __forceinline__ void dot2_ones(float& acc, int w) {          // acc +
 // D = 256 decoder block (multimae_utils.py:229-232, output_adapters.py:265-266) without its own pass over the residual stream.  The final
 // values stay in registers (where the accumulators were); per-row (sum, sum of squares) of a wave's 64 columns are reduced over the 16
 // lanes that share a row, exchanged through 8 KiB of LDS behind ONE workgroup barrier, and every wave normalises its own columns.
-template <int TM, bool AKS, bool BKS, int FL = 0, bool KF = false, bool UNR = false, bool WIDE = false, bool H16 = false, bool LNE = false>
+// LNS = false (gemm_bf16_pp_ln_nostat_kernel): the same side output without the ln_mean / ln_rstd stores -- a forward no backward follows.
+template <int TM, bool AKS, bool BKS, int FL = 0, bool KF = false, bool UNR = false, bool WIDE = false, bool H16 = false, bool LNE = false,
+          bool LNS = true>
 __device__ __forceinline__ void pp_body(const GemmArgs& g, const int v0, const int vstep) {
     constexpr int WMR = TM * 32;                         // output rows per wave
     constexpr int BM = 2 * WMR, BN = 256, NW = 8;
@@ -627,7 +629,9 @@ __device__ __forceinline__ void pp_body(const GemmArgs& g, const int v0, const i
                             const float rs = 1.0f / sqrtf(var + g.ln_eps);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) o[j] = (o[j] - mu) * rs * g4[j] + b4[j];
-                            if (wn == 0 && c16 == 0 && r < rows_left) { g.ln_mean[mw + r] = mu; g.ln_rstd[mw + r] = rs; }
+                            if constexpr (LNS) {
+                                if (wn == 0 && c16 == 0 && r < rows_left) { g.ln_mean[mw + r] = mu; g.ln_rstd[mw + r] = rs; }
+                            }
                         }
                         pk[u] = pack4_16<H16>(o);
                     }
@@ -693,7 +697,12 @@ __global__ void __launch_bounds__(512) gemm_bf16_pp_kernel(const GemmArgs g) {
     pp_body<TM, AKS, BKS, FL, KF, (FL != 0 && KF && !(TM == 5 && BKS)), false, H16, LNE>(g, blockIdx.x, gridDim.x);
 }
 
-template <int TM, bool AKS, bool BKS, int FL = 0, bool KF = false, bool H16 = false, bool LNE = false>
+template <int TM, bool AKS, bool BKS, int FL, bool KF>        // LNE without the statistics stores (LNS = false): bf16, the inference forward
+__global__ void __launch_bounds__(512) gemm_bf16_pp_ln_nostat_kernel(const GemmArgs g) {
+    pp_body<TM, AKS, BKS, FL, KF, (FL != 0 && KF && !(TM == 5 && BKS)), false, false, true, false>(g, blockIdx.x, gridDim.x);
+}
+
+template <int TM, bool AKS, bool BKS, int FL = 0, bool KF = false, bool H16 = false, bool LNE = false, bool LNS = true>
 int launch(const GemmArgs& g, int batch, hipStream_t st) {
     constexpr int BM = TM * 64, BN = 256;
     const int tiles_m = (g.M + BM - 1) / BM;
@@ -706,7 +715,8 @@ int launch(const GemmArgs& g, int batch, hipStream_t st) {
     const int gx = (env_persist && a.tiles_total > n_cu) ? n_cu : a.tiles_total;      // one resident workgroup per CU walks the tile list
     dim3 grid(gx, batch, a.splitk), block(512);
     const size_t lds = (size_t)4 * (BM + BN) * 64 + 1024 + (LNE ? (size_t)BM * 4 * 2 * 4 : 0);      // + the row-statistics exchange of the LayerNorm side output
-    return mmae_launch_lds<gemm_bf16_pp_kernel<TM, AKS, BKS, FL, KF, H16, LNE>>(grid, block, lds, st, "gemm_bf16_pp", a);
+    if constexpr (LNE && !LNS) return mmae_launch_lds<gemm_bf16_pp_ln_nostat_kernel<TM, AKS, BKS, FL, KF>>(grid, block, lds, st, "gemm_bf16_pp", a);
+    else return mmae_launch_lds<gemm_bf16_pp_kernel<TM, AKS, BKS, FL, KF, H16, LNE>>(grid, block, lds, st, "gemm_bf16_pp", a);
 }
 
 }  // namespace

@@ -14,7 +14,8 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // MXQ (bf16 y, D % 32 == 0): also write the MX-fp8 quantisation of the bf16 row (what mmae_mx_quant would make of y): a
 // 32-element block is the 8 adjacent lanes of one chunk round
-template <int NV, typename YT, bool MXQ = false>
+// STATS = false: the same kernel without the mean / rstd stores -- a forward that no backward follows (mmae_layernorm_fwd_nostat)
+template <int NV, typename YT, bool MXQ = false, bool STATS = true>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, YT* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd,
@@ -44,7 +45,9 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
     }
     const float var = wave_sum(q) / (float)D;
     const float rs = 1.0f / sqrtf(var + eps);
-    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+    if constexpr (STATS) {
+        if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+    }
     YT* yr = y + row * D;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -596,6 +599,27 @@ int mmae_layernorm_fwd(const float* x, const float* gamma, const float* beta, vo
     switch (nv) { case 1: LN_FWD(1) break; case 2: LN_FWD(2) break; case 3: LN_FWD(3) break; default: LN_FWD(4) break; }
 #undef LN_FWD
     return mmae_check_launch("layernorm_fwd");
+}
+
+int mmae_layernorm_fwd_nostat(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, int64_t R, int D, float eps,
+                              void* stream) {
+    MMAE_REQUIRE(x && gamma && beta && y, "layernorm_fwd_nostat: null pointer");
+    MMAE_REQUIRE(y_dtype == MMAE_BF16 || y_dtype == MMAE_F32, "layernorm_fwd_nostat: y is bf16 or f32");
+    MMAE_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "layernorm_fwd_nostat: D must be a multiple of 4 in [4,1024]");
+    MMAE_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)gamma % 16 == 0) && ((uintptr_t)beta % 16 == 0) && ((uintptr_t)y % 8 == 0),
+                 "layernorm_fwd_nostat: unaligned pointer");
+    if (R <= 0) return 0;
+    const int nv = (D + 255) / 256;
+    dim3 grid((unsigned)cdiv64(R, 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    float* const none = nullptr;
+#define LN_FWD_NS(NV)                                                                                                                          \
+    if (y_dtype == MMAE_BF16) hipLaunchKernelGGL((ln_fwd_kernel<NV, uint16_t, false, false>), grid, block, 0, st, x, gamma, beta, (uint16_t*)y, \
+                                                  none, none, (long long)R, D, eps);                                                            \
+    else hipLaunchKernelGGL((ln_fwd_kernel<NV, float, false, false>), grid, block, 0, st, x, gamma, beta, (float*)y, none, none, (long long)R, D, eps);
+    switch (nv) { case 1: LN_FWD_NS(1) break; case 2: LN_FWD_NS(2) break; case 3: LN_FWD_NS(3) break; default: LN_FWD_NS(4) break; }
+#undef LN_FWD_NS
+    return mmae_check_launch("layernorm_fwd_nostat");
 }
 
 int mmae_layernorm_fwd_mx(const float* x, const float* gamma, const float* beta, void* y_bf16, float* mean, float* rstd, int64_t R, int D,

@@ -218,7 +218,7 @@ static double gemm_algorithmic_bytes(const mmae_gemm_desc* d) {
     const double mn = (double)d->M * d->N * d->batch;
     double b = ((double)d->M * d->K + (double)d->N * d->K) * d->batch * eab + mn * ec;
     if (d->accumulate) b += mn * ec;
-    if (d->aux && d->epi != MMAE_EPI_NONE) b += mn * (d->aux_dtype == MMAE_F32 ? 4.0 : 2.0);
+    if (d->aux && d->epi != MMAE_EPI_NONE && d->epi != MMAE_EPI_GELU_Y) b += mn * (d->aux_dtype == MMAE_F32 ? 4.0 : 2.0);
     if (d->resid) b += mn * 4.0;
     if (d->ln_out) b += mn * 2.0;
     return b;
@@ -238,7 +238,11 @@ int mmae_gemm_ex(const mmae_gemm_desc* d, void* stream, int timing_cls, double f
     MMAE_REQUIRE(!d->aux || d->aux_dtype == MMAE_F32 || d->aux_dtype == (h16 ? MMAE_F16 : MMAE_BF16), "gemm: bad aux_dtype (16-bit aux: the operands' format)");
     if (h16 && (d->batch != 1 || d->split_k > 1 || d->a_colsum || d->a_trans)) { mmae_set_error("gemm(f16): unbatched, unsplit products with k-contiguous A only"); return MMAE_ESUPPORT; }
     MMAE_REQUIRE(!(d->accumulate && d->c_dtype != MMAE_F32), "gemm: accumulate needs f32 C");
-    MMAE_REQUIRE(!(d->epi != MMAE_EPI_NONE && !d->aux), "gemm: epilogue needs aux");
+    MMAE_REQUIRE(!(d->epi != MMAE_EPI_NONE && d->epi != MMAE_EPI_GELU_Y && !d->aux), "gemm: epilogue needs aux");
+    if (d->epi == MMAE_EPI_GELU_Y && (d->ab_dtype == MMAE_MXFP8 || h16 || !d->bias)) {
+        mmae_set_error("gemm: the one-stream GELU epilogue (MMAE_EPI_GELU_Y) needs a bias and bf16 or f32-class operands"); return MMAE_ESUPPORT;
+    }
+
     MMAE_REQUIRE(!(d->resid && d->batch != 1), "gemm: residual is unbatched only");
     GemmArgs g;
     g.A = d->A; g.B = d->B; g.C = d->C;
@@ -248,12 +252,13 @@ int mmae_gemm_ex(const mmae_gemm_desc* d, void* stream, int timing_cls, double f
     g.sAo = d->sA_outer; g.sAi = d->sA_inner; g.sBo = d->sB_outer; g.sBi = d->sB_inner;
     g.sCo = d->sC_outer; g.sCi = d->sC_inner;
     g.bias = d->bias; g.resid = d->resid; g.ldr = d->ldr;
-    g.aux = d->aux; g.ldaux = d->ldaux;
+    g.aux = d->epi == MMAE_EPI_GELU_Y ? nullptr : d->aux; g.ldaux = d->ldaux;
     g.c_f32 = d->c_dtype == MMAE_F32; g.aux_f32 = d->aux_dtype == MMAE_F32;
-    MMAE_REQUIRE(d->epi >= MMAE_EPI_NONE && d->epi <= MMAE_EPI_MUL, "gemm: bad epi");
-    // GELU_G / MUL are GELU / DGELU with aux holding the derivative: same kernels and flavours, one flag
-    g.aux_grad = (d->epi == MMAE_EPI_GELU_G || d->epi == MMAE_EPI_MUL) ? 1 : 0;
-    g.epi = d->epi == MMAE_EPI_GELU_G ? MMAE_EPI_GELU : (d->epi == MMAE_EPI_MUL ? MMAE_EPI_DGELU : d->epi);
+    MMAE_REQUIRE(d->epi >= MMAE_EPI_NONE && d->epi <= MMAE_EPI_GELU_Y, "gemm: bad epi");
+    // GELU_G / MUL are GELU / DGELU with aux holding the derivative: same kernels and flavours, one flag; GELU_Y is GELU without the aux
+    // stream (flag value 2: the generic kernels skip the store, the ping-pong kernel has a flavour of its own)
+    g.aux_grad = (d->epi == MMAE_EPI_GELU_G || d->epi == MMAE_EPI_MUL) ? 1 : (d->epi == MMAE_EPI_GELU_Y ? 2 : 0);
+    g.epi = (d->epi == MMAE_EPI_GELU_G || d->epi == MMAE_EPI_GELU_Y) ? MMAE_EPI_GELU : (d->epi == MMAE_EPI_MUL ? MMAE_EPI_DGELU : d->epi);
     g.accumulate = d->accumulate; g.alpha = d->alpha;
     g.tiles_n = 0;
     g.colpart = d->colsum_part;
@@ -273,7 +278,7 @@ int mmae_gemm_ex(const mmae_gemm_desc* d, void* stream, int timing_cls, double f
     if (d->ln_out) {
         const bool ok = (d->ab_dtype == MMAE_BF16 || h16) && d->c_dtype == MMAE_F32 && d->N == 256 && d->ldc == 256 && d->bias && d->epi == MMAE_EPI_NONE &&
                         !d->accumulate && d->batch == 1 && d->split_k <= 1 && !d->a_trans && !d->b_trans && (d->K % 32) == 0 && d->alpha == 1.0f &&
-                        !d->a_amax && (!d->ln_gamma || (d->ln_beta && d->ln_mean && d->ln_rstd)) && ((uintptr_t)d->ln_out % 16) == 0 &&
+                        !d->a_amax && (!d->ln_gamma || (d->ln_beta && !d->ln_mean == !d->ln_rstd)) && ((uintptr_t)d->ln_out % 16) == 0 &&
                         (!d->ln_gamma || (((uintptr_t)d->ln_gamma | (uintptr_t)d->ln_beta) % 16) == 0);
         if (!ok) { mmae_set_error("gemm: ln_out needs a 16-bit x 16-bit -> f32 product with bias [+ residual], N = ldc = 256, unbatched, unsplit, k-contiguous operands, K % 32 == 0"); return MMAE_ESUPPORT; }
     }
@@ -288,7 +293,7 @@ int mmae_gemm_ex(const mmae_gemm_desc* d, void* stream, int timing_cls, double f
                ((uintptr_t)d->C % 16 == 0);
     if (d->bias) vec = vec && ((uintptr_t)d->bias % 16 == 0);
     if (d->resid) vec = vec && (d->ldr % 4 == 0) && ((uintptr_t)d->resid % 16 == 0);
-    if (d->aux) vec = vec && (d->ldaux % 4 == 0) && ((uintptr_t)d->aux % 16 == 0);
+    if (d->aux || d->epi == MMAE_EPI_GELU_Y) vec = vec && (d->ldaux % 4 == 0) && ((uintptr_t)g.aux % 16 == 0);     // (GELU_Y: the routine its two-stream twin takes)
     g.vec = vec ? 1 : 0;
     MMAE_REQUIRE(!d->colsum_part || (vec && ((uintptr_t)d->colsum_part % 16 == 0)), "gemm: colsum_part needs 4-element aligned C/aux");
     hipStream_t st = (hipStream_t)stream;
@@ -318,6 +323,12 @@ int mmae_gemm_ex(const mmae_gemm_desc* d, void* stream, int timing_cls, double f
     int code = 0, unused = 0;
     gemm_plan(d, &code, &unused);
     if (d->ln_out) code = 9;                                // the 256 x 256 ping-pong tile: the only kernel with the LayerNorm side output
+    // the one-stream GELU is a compiled flavour of the ping-pong kernel and exists nowhere else: refuse before anything is launched
+    if (d->epi == MMAE_EPI_GELU_Y && !(d->ab_dtype == MMAE_BF16 && (code == 9 || code == 10) && !d->a_trans && !d->b_trans && (d->K % 32) == 0 &&
+                                       gemm_flavour(g, d->batch) == FL_BF16_BIAS_GELU_Y)) {
+        mmae_set_error("gemm: MMAE_EPI_GELU_Y exists as a flavour of the ping-pong kernel only (bf16 -> bf16, the shapes mmae_gemm_plan gives tile 9 / 10, K % 32 == 0, 8-aligned widths)");
+        return MMAE_ESUPPORT;
+    }
     g.acs = nullptr;
     if (h16) return mmae_gemm_bf16_pp_impl(d, g, 9, st);    // fp16 storage: the 256 x 256 ping-pong tile, compiled flavours only
     if (d->a_colsum) {

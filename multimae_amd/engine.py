@@ -120,6 +120,18 @@ def set_encoder_fanout(flag: bool) -> None:
     _state['encoder_fanout'] = bool(flag)
 
 
+def inference_forward() -> bool:
+    return _state.get('inference_forward', True)
+
+
+def set_inference_forward(flag: bool) -> None:
+    """Default on: an encoder stack called with nothing to differentiate (torch.no_grad(): every evaluate(), ModelEma evaluation, feature
+    extraction) runs mmae_stack_fwd_infer -- the training forward's kernels with the backward's side outputs compiled out, scratch for ONE
+    block, outputs bit-equal and owning their memory.  False = such a call runs the training forward (ops.stack_fwd) call for call: the A/B
+    handle of tests/test_infer_forward_gpu.py and tools/infer_forward_bench.py.  With gradients enabled the switch changes nothing."""
+    _state['inference_forward'] = bool(flag)
+
+
 def adapter_streams() -> bool:
     return _state['adapter_streams']
 

@@ -346,7 +346,22 @@ def _grad_targets(sink: GradSink, params: Sequence[Optional[Tensor]]):
     return dsts, direct
 
 
-class EncoderStackFn(torch.autograd.Function):
+class _RecordingAtApply:
+    """Mixin of an autograd.Function whose first argument is a _Cfg: notes in cfg.recording whether the call can record a node.
+    forward() itself cannot tell: it always runs with grad mode off, and ctx.needs_input_grad reports requires_grad of the inputs in
+    either mode -- only where apply() is called is torch.no_grad() visible."""
+
+    @classmethod
+    def apply(cls, cfg, *args):
+        cfg.recording = torch.is_grad_enabled()
+        return super().apply(cfg, *args)
+
+
+def _nothing_to_differentiate(ctx, cfg) -> bool:
+    return not (getattr(cfg, 'recording', True) and any(ctx.needs_input_grad))
+
+
+class EncoderStackFn(_RecordingAtApply, torch.autograd.Function):
     """L transformer blocks in one autograd node.  forward(cfg, x[B,N,D] f32, *params(12 per layer))
 
     cfg: act, wc, heads, eps, all_layers, on_layer_done; optional dp (2 L per-sample stochastic-depth scale tensors or None
@@ -364,8 +379,16 @@ class EncoderStackFn(torch.autograd.Function):
         ctx.cfg, ctx.params, ctx.shape = cfg, params, (B, N, D)
         ctx.stack, ctx.saved = None, None
         if drops is None and ops.stack_composites() and L <= 64 and ops.block_composite_ok(h, cfg.act, cfg.heads, N):
-            outs, state = ops.stack_fwd(h, params, cfg.wc, cfg.heads, cfg.eps, cfg.act, B, N, dp,
-                                        mx=bool(getattr(cfg, 'mx', False)) and N <= 256)      # beyond 256 tokens: bf16 products, as the per-kernel route ran them
+            mx = bool(getattr(cfg, 'mx', False)) and N <= 256     # beyond 256 tokens: bf16 products, as the per-kernel route ran them
+            # nothing to differentiate (torch.no_grad(): evaluation, EMA evaluation, feature extraction), no stochastic depth, no MX
+            # products: the forward without the backward's side outputs -- same kernels, bit-equal outputs that own their memory
+            if (_nothing_to_differentiate(ctx, cfg) and engine.inference_forward() and (dp is None or all(t is None for t in dp))
+                    and not (mx and ops.mx_stack_ok(D, params[8].shape[0], cfg.act))):
+                outs = ops.stack_fwd_infer(h, params, cfg.wc, cfg.heads, cfg.eps, cfg.act, B, N, 'all_layers' if cfg.all_layers else 'last')
+                if cfg.all_layers:
+                    return tuple(o.view(B, N, D) for o in outs)
+                return outs[-1].view(B, N, D)
+            outs, state = ops.stack_fwd(h, params, cfg.wc, cfg.heads, cfg.eps, cfg.act, B, N, dp, mx=mx)
             ctx.stack = state if save else None
             if cfg.all_layers:
                 return tuple(o.view(B, N, D) for o in outs)

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 import contextlib
 
-from ._lib import BF16, F16, F32, F32X3, F32F16, MXFP8, EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_G, EPI_MUL, AdapterDesc, BlockDesc, DwGroupDesc, GemmDesc, OptDesc, OptGroupsDesc, PatchSrc, StackDesc, check
+from ._lib import BF16, F16, F32, F32X3, F32F16, MXFP8, EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_G, EPI_MUL, EPI_GELU_Y, AdapterDesc, BlockDesc, DwGroupDesc, GemmDesc, OptDesc, OptGroupsDesc, PatchSrc, StackDesc, check
 
 Tensor = torch.Tensor
 
@@ -118,6 +118,8 @@ def gemm(A: Tensor, B: Tensor, C: Tensor, M: int, N: int, K: int, *, lda: int, l
     d.resid, d.ldr = _p(resid), ldr
     d.aux, d.ldaux = _p(aux), ldaux
     d.aux_dtype = dcode(aux.dtype) if aux is not None else F32
+    if epi == EPI_GELU_Y:                                 # no aux stream; the GELU routine is its two-stream twin's, whose aux has C's dtype
+        d.aux, d.aux_dtype = None, dcode(C.dtype)
     d.epi, d.accumulate, d.alpha, d.tile = epi, int(accumulate), alpha, tile
     if ln is not None:
         gam, bet, lo, lm, lr, le = ln
@@ -577,6 +579,17 @@ def mx_stack_ok(D: int, Hd: int, act: torch.dtype) -> bool:
     return act == torch.bfloat16 and D % 256 == 0 and Hd % 256 == 0
 
 
+def _stack_tables(params: Sequence[Tensor], wc, L: int, act: torch.dtype):
+    """(act-dtype weights, mmae_stack_desc.w, mmae_stack_desc.p) of a stack: the pointer tables cached per parameter list, shared by
+    stack_fwd and stack_fwd_infer"""
+    wts = [wc(params[12 * l + i]) for l in range(L) for i in (2, 4, 8, 10)]
+    probe = (wts[0].data_ptr(), wts[-1].data_ptr(), params[0].data_ptr(), params[-1].data_ptr())
+    w_arr, p_arr = _PTRS.get(('stack', id(params[0]), L, act), probe, lambda: (
+        _ptr_arr([w.data_ptr() for w in wts]),
+        _ptr_arr([params[12 * l + i].data_ptr() for l in range(L) for i in (0, 1, 3, 5, 6, 7, 9, 11)])))
+    return wts, w_arr, p_arr
+
+
 def stack_fwd(x: Tensor, params: Sequence[Tensor], wc, heads: int, eps: float, act: torch.dtype, B: int, N: int,
               dp: Optional[Sequence[Optional[Tensor]]] = None, mx: bool = False):
     """L = len(params) // 12 pre-LN blocks on x f32 [B*N, D] in one library call.
@@ -590,11 +603,7 @@ def stack_fwd(x: Tensor, params: Sequence[Tensor], wc, heads: int, eps: float, a
     d = StackDesc()
     d.L, d.B, d.N, d.D, d.heads, d.Hd = L, B, N, D, heads, Hd
     d.act_dtype, d.f32_gemm, d.eps = dcode(act), _f32_code(), eps
-    wts = [wc(params[12 * l + i]) for l in range(L) for i in (2, 4, 8, 10)]
-    probe = (wts[0].data_ptr(), wts[-1].data_ptr(), params[0].data_ptr(), params[-1].data_ptr())
-    w_arr, p_arr = _PTRS.get(('stack', id(params[0]), L, act), probe, lambda: (
-        _ptr_arr([w.data_ptr() for w in wts]),
-        _ptr_arr([params[12 * l + i].data_ptr() for l in range(L) for i in (0, 1, 3, 5, 6, 7, 9, 11)])))
+    wts, w_arr, p_arr = _stack_tables(params, wc, L, act)
     d.w, d.p = ctypes.cast(w_arr, ctypes.c_void_p), ctypes.cast(p_arr, ctypes.c_void_p)
     dp_arr = None
     if dp is not None and any(t is not None for t in dp):
@@ -621,6 +630,37 @@ def stack_fwd(x: Tensor, params: Sequence[Tensor], wc, heads: int, eps: float, a
     s = StackState()
     s.desc, s.act, s.keep, s.x, s.L, s.shape, s.act_dtype, s.dp = d, slab, (w_arr, p_arr, dp_arr, wts, dp, mxw), x, L, (B, N, D, Hd), act, dp
     return outs, s
+
+
+def stack_fwd_infer(x: Tensor, params: Sequence[Tensor], wc, heads: int, eps: float, act: torch.dtype, B: int, N: int,
+                    keep='last') -> list:
+    """stack_fwd for a call that no backward follows (mmae_stack_fwd_infer): the same kernels with the backward's side outputs compiled
+    out, bit-equal outputs.  keep: 'all_layers', 'last', or the indices of the blocks whose output is wanted (the last is always kept).
+    Returns the kept outputs in layer order as f32 [B*N, D] tensors that own their memory; the scratch (one block's activations,
+    mmae_stack_infer_bytes: independent of the depth) is released to the caching allocator on return -- stream-ordered, like any
+    temporary."""
+    lib = _lib.load()
+    R, D = x.shape
+    L = len(params) // 12
+    Hd = params[8].shape[0]
+    d = StackDesc()
+    d.L, d.B, d.N, d.D, d.heads, d.Hd = L, B, N, D, heads, Hd
+    d.act_dtype, d.f32_gemm, d.eps = dcode(act), _f32_code(), eps
+    wts, w_arr, p_arr = _stack_tables(params, wc, L, act)
+    d.w, d.p = ctypes.cast(w_arr, ctypes.c_void_p), ctypes.cast(p_arr, ctypes.c_void_p)
+    d.x = x.data_ptr()
+    kept = set(range(L)) if keep == 'all_layers' else ({L - 1} if keep == 'last' else {int(l) for l in keep} | {L - 1})
+    assert all(0 <= l < L for l in kept), kept
+    outs = {l: torch.empty((R, D), device=x.device, dtype=torch.float32) for l in sorted(kept)}
+    o_arr = _ptr_arr([outs[l].data_ptr() if l in outs else None for l in range(L)])
+    slab = _slab(lib.mmae_stack_infer_bytes(ctypes.byref(d)), x.device)
+    d.act, d.act_bytes = slab.data_ptr(), slab.numel()
+    st = _stream()
+    ws = stream_workspace(st, x.device)
+    d.ws_main, d.ws_main_elems = ws.data_ptr(), ws.numel()
+    check(lib.mmae_stack_fwd_infer(ctypes.byref(d), ctypes.cast(o_arr, ctypes.c_void_p), st), 'stack_fwd_infer')
+    del wts                                               # (alive until here: the call reads the act-dtype weights)
+    return [outs[l] for l in sorted(kept)]
 
 
 def stack_bwd(s: StackState, d_outs: Sequence[Optional[Tensor]], grads: Sequence[Optional[Tensor]], grad_acc: bool,
