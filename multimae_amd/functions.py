@@ -248,9 +248,7 @@ def block_bwd(dx: Tensor, dx_act: Tensor, fc2b_done: bool, saved, P: Sequence[Te
     s1, s2 = dp
     dropping = k_proj is not None or len(Pm) > 3
     if s1 is None and s2 is None and not dropping and Pm[0] == 'fused' and ops.block_composite_ok(x0, act, heads, N):
-        out = _block_bwd_composite(dx, dx_act, fc2b_done, saved, P, wc, sink, heads, act, B, N, cs_param)
-        if out is not None:
-            return out
+        return _block_bwd_composite(dx, dx_act, fc2b_done, saved, P, wc, sink, heads, act, B, N, cs_param)
     # MLP: x2 = x1 + s2[b] * mlp(norm2(x1)); the branch sees the per-sample rescaled gradient
     if k_out is not None:                                   # the gradient through fc2's dropout (and the branch's stochastic-depth scale)
         dm_act = ops.dropout_apply(dx, k_out, inv, out_dtype=act, row_scale=s2, per=N * D)
@@ -304,22 +302,73 @@ def _block_bwd_composite(dx, dx_act, fc2b_done, saved, P, wc, sink: GradSink, he
     activations that forward left GELU'(pre-activation) in `hpre`, which the per-op dGELU epilogue would differentiate again
     (ADVICE r3)."""
     n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b = P
-    dsts, acc = _grad_targets(sink, list(P) + [cs_param])
-    if acc:                                             # accumulating straight into the arena: later composites of this epoch must accumulate too
-        for p in list(P) + [cs_param]:
-            if p is not None and p.requires_grad:
-                engine.mark_written(p)
-    use_side = sink.side is not None and acc
-    dx0, dx0_act, keep = ops.block_bwd_composite(dx, dx_act, fc2b_done, saved, P, (wc(qkvw), wc(projw), wc(fc1w), wc(fc2w)), dsts[:12],
-                                                 dsts[12], acc, heads, act, B, N, sink.side.cuda_stream if use_side else None)
-    if use_side:
-        engine.mark_side_dirty(sink.side)
-        engine.keep_until_join(keep)
-    if acc:
-        return dx0, dx0_act, None, (None,) * 12
+    # (the block form never stores on a first write: it accumulates onto the zeroed arena and marks its parameters written)
+    (dx0, dx0_act), grads, _ = _composite_bwd(sink, list(P) + [cs_param], store_first=False, launch=lambda dsts, acc, grad_acc, side: (
+        ops.block_bwd_composite(dx, dx_act, fc2b_done, saved, P, (wc(qkvw), wc(projw), wc(fc1w), wc(fc2w)), dsts[:12], dsts[12], grad_acc, heads,
+                                act, B, N, side)))
     if fc2b_done:
-        dsts[11] = None
-    return dx0, dx0_act, dsts[12], tuple(dsts[:12])
+        grads[11] = None
+    return dx0, dx0_act, grads[12], tuple(grads[:12])
+
+
+def _dp_of(dp, l: int):
+    return (None, None) if dp is None else (dp[2 * l], dp[2 * l + 1])
+
+
+def blocks_fwd(h: Tensor, blocks: Sequence[Tensor], wc, heads: int, eps: float, act, B: int, N: int, save: bool, dp=None, drops=None,
+               all_layers: bool = False):
+    """A chain of len(blocks) // 12 transformer blocks, one block_fwd each.  dp: two stochastic-depth scale tensors (or None) per block,
+    or None; drops: (attn_drop, drop) per block, or None.  Returns (output, [what block_bwd needs, per block], [every block's output]
+    when all_layers)."""
+    saved, outs = [], []
+    for l in range(len(blocks) // 12):
+        h, s = block_fwd(h, blocks[12 * l:12 * l + 12], wc, heads, eps, act, B, N, save, _dp_of(dp, l), drop=(0., 0.) if drops is None else drops[l])
+        saved.append(s)
+        if all_layers:
+            outs.append(h)
+    return h, saved, outs
+
+
+def blocks_bwd(dx: Optional[Tensor], dx_act: Optional[Tensor], saved: list, blocks: Sequence[Tensor], wc, sink: GradSink, heads: int, act,
+               B: int, N: int, dp=None, drops=None, d_outs: Optional[Sequence[Optional[Tensor]]] = None, below: Optional[Tensor] = None,
+               on_layer_done=None):
+    """Backward of blocks_fwd, one block_bwd each, from the top down.  dx / dx_act: the gradient of the chain's output as f32 and in
+    the activation dtype (None: it arrives through d_outs); d_outs[l]: gradient of block l's own output (a forward with all_layers),
+    added before block l runs; below: the bias of the Linear that produced the chain's input, when its gradient is the column sums of
+    the chain's input gradient (an adapter's MLP in front of its blocks); on_layer_done(l): called when every gradient of block l went
+    straight into the arena.  Frees saved[l] on the way.
+    Returns (dx, dx_act, 12 gradients per block, `below`'s gradient was delivered, that gradient or None when it went into the arena)."""
+    depth = len(blocks) // 12
+    grads: List[Optional[Tensor]] = [None] * (12 * depth)
+    fc2b_done, g_cs = False, None
+    for l in reversed(range(depth)):
+        dl = d_outs[l] if d_outs is not None else None
+        if dl is not None:
+            dx = dl if dx is None else ops.axpy_(dx, dl, 1.0)
+            dx_act = None
+        if dx is None:
+            continue
+        if dx_act is None:
+            dx_act = ops.cast(dx, act)
+        # the bias gradient of block l-1's fc2 (column sums of this block's input gradient) rides along with this block's LayerNorm-1
+        # reduction -- unless more gradient is added to dx before block l-1 sees it (d_outs), block l-1's MLP branch was rescaled per
+        # sample (stochastic depth: colsum(dx0) is not its fc2 bias gradient) or its fc2 output went through nn.Dropout
+        if l == 0:
+            cs_param = below
+        elif d_outs is not None or _dp_of(dp, l - 1)[1] is not None or (drops is not None and drops[l - 1][1] > 0.):
+            cs_param = None
+        else:
+            cs_param = blocks[12 * (l - 1) + 11]
+        dx, dx_act, g_cs_next, g = block_bwd(dx, dx_act, fc2b_done, saved[l], blocks[12 * l:12 * l + 12], wc, sink, heads, act, B, N, cs_param,
+                                             _dp_of(dp, l))
+        grads[12 * l:12 * l + 12] = g
+        if fc2b_done:
+            grads[12 * l + 11] = g_cs
+        fc2b_done, g_cs = cs_param is not None and cs_param.requires_grad, g_cs_next
+        saved[l] = None
+        if on_layer_done is not None and all(x is None for x in grads[12 * l:12 * l + 12]):
+            on_layer_done(l)                             # every gradient of the layer went straight into the arena
+    return dx, dx_act, grads, fc2b_done, g_cs
 
 
 class _Cfg:
@@ -344,6 +393,31 @@ def _grad_targets(sink: GradSink, params: Sequence[Optional[Tensor]]):
         else:
             dsts.append(torch.empty(p.shape, device=p.device, dtype=torch.float32))
     return dsts, direct
+
+
+def _composite_bwd(sink: GradSink, params: Sequence[Optional[Tensor]], launch, store_first: bool = True):
+    """The protocol around ONE composite backward call (mmae_stack_bwd, mmae_block_bwd, mmae_adapter_bwd) that writes the gradients of
+    `params`: destinations and the one accumulate flag that describes them (_grad_targets); the weight-gradient side stream when there
+    is one and the gradients go straight into the arena; the library's own flag -- store_first: the first write of these parameters
+    since zero_grad() stores instead of accumulating onto zeros (engine.claim_first_write), else the parameters are marked written and
+    the call accumulates; afterwards the side stream is marked dirty and what it may still read is kept until the join.
+    launch(dsts, acc, grad_acc, side stream handle or None) -> (*results, keep-alives), as the entry points of ops return them.
+    Returns ([results], what goes back to autograd per parameter: None when it went into the arena, else the fresh tensor, acc)."""
+    dsts, acc = _grad_targets(sink, params)
+    use_side = sink.side is not None and acc
+    if store_first:
+        grad_acc = acc and not engine.claim_first_write(params)
+    else:
+        grad_acc = acc
+        if acc:                                         # later composites of this epoch must accumulate too
+            for p in params:
+                if p is not None and p.requires_grad:
+                    engine.mark_written(p)
+    *result, keep = launch(dsts, acc, grad_acc, sink.side.cuda_stream if use_side else None)
+    if use_side:
+        engine.mark_side_dirty(sink.side)
+        engine.keep_until_join(keep)
+    return result, ([None] * len(params) if acc else dsts), acc
 
 
 class _RecordingAtApply:
@@ -393,17 +467,9 @@ class EncoderStackFn(_RecordingAtApply, torch.autograd.Function):
             if cfg.all_layers:
                 return tuple(o.view(B, N, D) for o in outs)
             return outs[-1].view(B, N, D)
-        saved, outs = [], []
-        for l in range(L):
-            dpl = (None, None) if dp is None else (dp[2 * l], dp[2 * l + 1])
-            h, s = block_fwd(h, params[12 * l:12 * l + 12], cfg.wc, cfg.heads, cfg.eps, cfg.act, B, N, save, dpl,
-                             drop=(0., 0.) if drops is None else drops[l])
-            saved.append(s)
-            if cfg.all_layers:
-                outs.append(h.view(B, N, D))
-        ctx.saved = saved
+        h, ctx.saved, outs = blocks_fwd(h, params, cfg.wc, cfg.heads, cfg.eps, cfg.act, B, N, save, dp, drops, cfg.all_layers)
         if cfg.all_layers:
-            return tuple(outs)
+            return tuple(o.view(B, N, D) for o in outs)
         return h.view(B, N, D)
 
     @staticmethod
@@ -412,72 +478,40 @@ class EncoderStackFn(_RecordingAtApply, torch.autograd.Function):
         B, N, D = ctx.shape
         L = len(params) // 12
         sink = GradSink(engine.direct_grads())
-        dp = getattr(cfg, 'dp', None)
-        if ctx.stack is not None:
-            d_outs: List[Optional[Tensor]] = [None] * L
-            for l in range(L):
-                dl = douts[l] if cfg.all_layers else (douts[0] if l == L - 1 else None)
-                if dl is not None:
-                    d_outs[l] = dl.contiguous().view(B * N, D)
-            if d_outs[L - 1] is None:                       # nothing reached the last block: zero gradient there
-                d_outs[L - 1] = torch.zeros((B * N, D), device=params[0].device, dtype=torch.float32)
-            dsts, acc = _grad_targets(sink, params)
-            use_side = sink.side is not None and acc
-            # first write since zero_grad(): the library stores instead of accumulating onto zeros (engine.claim_first_write)
-            lib_acc = acc and not engine.claim_first_write(params)
-            chunks, on_chunk = None, None
-            # readiness reports only when the gradients really are final in the arena at that point: with fresh tensors handed to
-            # autograd (acc False) AccumulateGrad writes them later, and a bucket reduced now would miss them
-            if cfg.on_layer_done is not None and acc:
-                c = max(1, int(getattr(cfg, 'bwd_chunk', 1) or 1))
-                chunks = [(max(0, hi - c), hi) for hi in range(L, 0, -c)]
-
-                def on_chunk(lo, hi):
-                    for l in reversed(range(lo, hi)):
-                        cfg.on_layer_done(l)
-            side_cus = engine.enc_bwd_side_cus() if use_side else 0       # A/B switch: dX chain and weight gradients side by side
-            prev_side = ops.gemm_side_cus(side_cus) if side_cus > 0 else 0
-            try:
-                dx, keep = ops.stack_bwd(ctx.stack, d_outs, dsts, lib_acc, sink.side.cuda_stream if use_side else None, chunks, on_chunk)
-            finally:
-                if side_cus > 0:
-                    ops.gemm_side_cus(prev_side)
-            ctx.stack = None
-            if use_side:
-                engine.mark_side_dirty(sink.side)
-                engine.keep_until_join(keep)
-            grads = [None] * (12 * L) if acc else dsts
-            return (None, dx.view(B, N, D), *grads)
-        grads: List[Optional[Tensor]] = [None] * (12 * L)
-        dx, dx_act = None, None
-        fc2b_done, g_cs = False, None
-        for l in reversed(range(L)):
+        d_outs: List[Optional[Tensor]] = [None] * L
+        for l in range(L):
             dl = douts[l] if cfg.all_layers else (douts[0] if l == L - 1 else None)
             if dl is not None:
-                dl = dl.contiguous().view(B * N, D)
-                dx = dl if dx is None else ops.axpy_(dx, dl, 1.0)
-                dx_act = None
-            if dx is None:
-                continue
-            if dx_act is None:
-                dx_act = ops.cast(dx, cfg.act)
-            # the bias gradient of block l-1's fc2 (column sums of this block's input gradient) rides along with this
-            # block's LayerNorm-1 reduction -- unless more gradient is added to dx before block l-1 sees it (all_layers) or
-            # block l-1's MLP branch was rescaled per sample (stochastic depth)
-            below_scaled = dp is not None and l > 0 and dp[2 * (l - 1) + 1] is not None
-            drops = getattr(cfg, 'drops', None)
-            below_dropped = drops is not None and l > 0 and drops[l - 1][1] > 0.       # block l-1's fc2 output went through nn.Dropout
-            cs_param = params[12 * (l - 1) + 11] if (l > 0 and not cfg.all_layers and not below_scaled and not below_dropped) else None
-            dpl = (None, None) if dp is None else (dp[2 * l], dp[2 * l + 1])
-            dx, dx_act, g_cs_next, g = block_bwd(dx, dx_act, fc2b_done, ctx.saved[l], params[12 * l:12 * l + 12], cfg.wc, sink,
-                                                 cfg.heads, cfg.act, B, N, cs_param, dpl)
-            grads[12 * l:12 * l + 12] = g
-            if fc2b_done:
-                grads[12 * l + 11] = g_cs
-            fc2b_done, g_cs = cs_param is not None and cs_param.requires_grad, g_cs_next
-            ctx.saved[l] = None
-            if cfg.on_layer_done is not None and all(x is None for x in grads[12 * l:12 * l + 12]):
-                cfg.on_layer_done(l)                         # every gradient of the layer went straight into the arena
+                d_outs[l] = dl.contiguous().view(B * N, D)
+        if ctx.stack is not None:
+            if d_outs[L - 1] is None:                       # nothing reached the last block: zero gradient there
+                d_outs[L - 1] = torch.zeros((B * N, D), device=params[0].device, dtype=torch.float32)
+
+            def launch(dsts, acc, grad_acc, side):
+                chunks, on_chunk = None, None
+                # readiness reports only when the gradients really are final in the arena at that point: with fresh tensors handed to
+                # autograd (acc False) AccumulateGrad writes them later, and a bucket reduced now would miss them
+                if cfg.on_layer_done is not None and acc:
+                    c = max(1, int(getattr(cfg, 'bwd_chunk', 1) or 1))
+                    chunks = [(max(0, hi - c), hi) for hi in range(L, 0, -c)]
+
+                    def on_chunk(lo, hi):
+                        for l in reversed(range(lo, hi)):
+                            cfg.on_layer_done(l)
+                side_cus = engine.enc_bwd_side_cus() if side is not None else 0       # A/B switch: dX chain and weight gradients side by side
+                prev_side = ops.gemm_side_cus(side_cus) if side_cus > 0 else 0
+                try:
+                    return ops.stack_bwd(ctx.stack, d_outs, dsts, grad_acc, side, chunks, on_chunk)
+                finally:
+                    if side_cus > 0:
+                        ops.gemm_side_cus(prev_side)
+            (dx,), grads, _ = _composite_bwd(sink, params, launch)
+            ctx.stack = None
+            return (None, dx.view(B, N, D), *grads)
+        # (without all_layers the only gradient is the last block's: the chain's own)
+        dx, _, grads, _, _ = blocks_bwd(None if cfg.all_layers else d_outs[-1], None, ctx.saved, params, cfg.wc, sink, cfg.heads, cfg.act, B, N,
+                                        getattr(cfg, 'dp', None), getattr(cfg, 'drops', None), d_outs if cfg.all_layers else None,
+                                        on_layer_done=cfg.on_layer_done)
         return (None, dx.view(B, N, D), *grads)
 
 
@@ -651,6 +685,27 @@ def _f32_mode(cfg) -> str:
     return 'f16' if m == 'h16' else m
 
 
+def _lazy_image(src: Tensor, write):
+    """The deferred writer of a prediction image that nothing on the training path reads (lazy.LazyPrediction fills it on first use):
+    write(src, dst) runs then, ordered behind the stream that produces `src` now.  The closure holds `src` alone -- an adapter's
+    prediction rows, a head's logits -- not the activations around it."""
+    ev = torch.cuda.current_stream().record_event() if src.is_cuda else None
+
+    def fill(dst):
+        if ev is not None:
+            cur = torch.cuda.current_stream()
+            cur.wait_event(ev)
+            src.record_stream(cur)                   # written on the producer's stream, read here on the consumer's
+        write(src, dst)
+    return fill
+
+
+def _adapter_params(params: Sequence[Tensor], T: int, depth: int):
+    """SpatialAdapterFn's parameters by role: mask_token, [T task embeddings], the 16 of the cross attention and its MLP, [12 per block],
+    out_proj.{weight, bias}, proj_context.{weight, bias}"""
+    return (params[0], params[1:1 + T], *params[1 + T:17 + T], params[17 + T:17 + T + 12 * depth], *params[17 + T + 12 * depth:])
+
+
 class SpatialAdapterFn(torch.autograd.Function):
     """forward(cfg, enc[B,NC,Denc] f32, ids_keep, ids_restore, *params)
 
@@ -689,36 +744,34 @@ class SpatialAdapterFn(torch.autograd.Function):
         B, NC, Denc = enc.shape
         n_keep = NC - G
         n_q = cfg.nh * cfg.nw if cfg.q_task < 0 else cfg.task_offsets[cfg.q_task + 1] - cfg.task_offsets[cfg.q_task]
-        mask_token = params[0]
-        temb = params[1:1 + T]
-        (qw, qb, kvw, kvb, pw_, pb, cnw, cnb, qnw, qnb, onw, onb, f1w, f1b, f2w, f2b) = params[1 + T:17 + T]
-        blocks = params[17 + T:17 + T + 12 * cfg.depth]
-        ow, ob, pcw, pcb = params[17 + T + 12 * cfg.depth:]
+        (mask_token, temb, qw, qb, kvw, kvb, pw_, pb, cnw, cnb, qnw, qnb, onw, onb, f1w, f1b, f2w, f2b, blocks, ow, ob, pcw,
+         pcb) = _adapter_params(params, T, cfg.depth)
         dev = enc.device
         save = any(ctx.needs_input_grad)
+        ctx.cfg, ctx.params, ctx.ids = cfg, params, (ids_keep, ids_restore)
+        ctx.dims = (B, NC, Denc, n_keep, n_q, T)
+        ctx.comp = None
 
         enc2 = enc.contiguous().view(B * NC, Denc)
         enc_act = getattr(cfg, 'enc_act', None)      # act-dtype copy shared by all adapters of one forward (MultiMAE.forward)
         if enc_act is None or enc_act.dtype != act or enc_act.shape != enc2.shape:
             enc_act = None
-        ctx.comp = None
         KP = cfg.C * cfg.ph * cfg.pw
         xattn = bool(getattr(cfg, 'use_xattn', True))
         # fp32 adapter, engine.set_fp32_adapter_gemm('h16'): activations / saved tensors / gradients of the composite call stored as fp16
         # (mmae.h MMAE_F16) -- the bf16 pipeline's kernels and traffic with TF32's significand; residual stream, statistics, losses f32
         h16 = (act == torch.float32 and getattr(cfg, 'f32_gemm', 'exact') == 'h16' and xattn
                and ops.adapter_h16_ok(enc2, heads, D, f1w.shape[0], n_q, NC, cfg.depth, T, KP))
-        ctx.h16 = h16
         # stochastic depth in decoder_transformer (SpatialOutputAdapter(drop_path_rate > 0), training): per-sample scales [(attention
         # branch, MLP branch)] * depth; the one-call adapter has no such option, the per-block sequence below folds them into the residual adds
         dps = getattr(cfg, 'dp', None)
-        dp_of = (lambda l: (dps[2 * l], dps[2 * l + 1])) if dps is not None else (lambda l: (None, None))
         # nn.Dropout sites (SpatialOutputAdapter(drop_rate / attn_drop_rate > 0), training): cfg.drops = (attn_drop, drop) -- the cross
         # attention's probabilities and proj output (output_adapters.py:118-119), the three sites of every decoder block (:131-132)
         drops = getattr(cfg, 'drops', None)
         p_attn, p_drop = drops if drops is not None else (0., 0.)
         if dps is not None or drops is not None:
-            h16 = ctx.h16 = False
+            h16 = False
+        ctx.h16 = h16
         if xattn and dps is None and drops is None and (h16 or ops.adapter_composite_ok(enc2, act, heads, D, n_q, NC, cfg.depth, T, KP)):
             # the whole adapter as ONE library call (same kernels, same order)
             w_list = [wc(qw), wc(kvw), wc(pw_), wc(f1w), wc(f2w)] + [wc(blocks[12 * l + i]) for l in range(cfg.depth) for i in (2, 4, 8, 10)] \
@@ -736,19 +789,10 @@ class SpatialAdapterFn(torch.autograd.Function):
                                          [None if t is None else t.detach().reshape(D) for t in temb], want_img=not lazy_img, store=store)
             if lazy_img:
                 img = torch.empty((B, cfg.C, cfg.nh * cfg.ph, cfg.nw * cfg.pw), device=enc.device, dtype=torch.float32)
-                ev = torch.cuda.current_stream().record_event() if enc.is_cuda else None
-                pat, geom = state.pat, (B, cfg.C, cfg.nh, cfg.nw, cfg.ph, cfg.pw)
-
-                def fill(dst, pat=pat, ev=ev, geom=geom):     # holds the prediction ROWS (their own allocation), not the activation slab
-                    if ev is not None:
-                        cur = torch.cuda.current_stream()
-                        cur.wait_event(ev)
-                        pat.record_stream(cur)               # written on the adapter's stream, read here on the consumer's
-                    ops.unpatchify_into(pat, dst, *geom)
-                cfg.lazy_fill = fill
+                geom = (B, cfg.C, cfg.nh, cfg.nw, cfg.ph, cfg.pw)
+                # holds the prediction ROWS (their own allocation), not the activation slab
+                cfg.lazy_fill = _lazy_image(state.pat, lambda pat, dst: ops.unpatchify_into(pat, dst, *geom))
             ctx.comp = state if save else None
-            ctx.cfg, ctx.params, ctx.ids = cfg, params, (ids_keep, ids_restore)
-            ctx.dims = (B, NC, Denc, n_keep, n_q, T)
             if save and engine.patch_domain_loss():
                 cfg.handle = PatHandle(state.pat, cfg.C, cfg.nh, cfg.nw, cfg.ph, cfg.pw, torch.float16 if h16 else act)
                 if h16 or (act == torch.float32 and getattr(cfg, 'f32_gemm', 'exact') == 'f16'):
@@ -763,48 +807,32 @@ class SpatialAdapterFn(torch.autograd.Function):
                 te[i].copy_(t.detach().reshape(D))
         queries, context = ops.decoder_build(ctx_tok, ids_keep, ids_restore, mask_token.detach().reshape(D), te, cfg.pos,
                                              cfg.task_offsets, cfg.q_task, B, n_keep, G, D, n_q)   # :183-234
-        if not xattn:                                # use_xattn=False (output_adapters.py:264-268): x = queries
-            h, bsaved = queries, []
-            for l in range(cfg.depth):
-                h, s = block_fwd(h, blocks[12 * l:12 * l + 12], wc, heads, eps, act, B, n_q, save, dp=dp_of(l), drop=(p_attn, p_drop))
-                bsaved.append(s)
-            h_act = ops.cast(h, act)
-            pat = _lin_fwd(h_act, ow, ob, wc, torch.float32)
-            img = ops.unpatchify(pat, B, cfg.C, cfg.nh, cfg.nw, cfg.ph, cfg.pw)
-            if save:
-                ctx.saved = (enc_act, context.shape, h_act, bsaved)
-            ctx.cfg, ctx.params, ctx.ids = cfg, params, (ids_keep, ids_restore)
-            ctx.dims = (B, NC, Denc, n_keep, n_q, T)
-            return img
-        qn, qmean, qrstd = ops.layernorm_fwd(queries, qnw, qnb, eps, act)
-        cn, cmean, crstd = ops.layernorm_fwd(context, cnw, cnb, eps, act)
-        q = _lin_fwd(qn, qw, qb, wc, act)
-        kv = _lin_fwd(cn, kvw, kvb, wc, act)
-        hd = D // heads
-        xo = torch.empty((B * n_q, D), device=dev, dtype=act)
-        Pm = ops.attention_fwd(AttnView(q, 0, D, n_q), AttnView(kv, 0, 2 * D, NC), AttnView(kv, D, 2 * D, NC),
-                               AttnView(xo, 0, D, n_q), B, heads, hd, hd ** -0.5, drop_p=p_attn)
-        x = _lin_fwd(xo, pw_, pb, wc, torch.float32)                                    # :265, no residual
-        k_x = None
-        if p_drop > 0.:                                                                 # CrossAttention.proj_drop (multimae_utils.py:213)
-            k_x = ops._dropout_keep((B * n_q, D), p_drop, dev)
-            x = ops.dropout_apply(x, k_x, 1.0 / (1.0 - p_drop), out=x)
-        on, omean, orstd = ops.layernorm_fwd(x, onw, onb, eps, act)
-        hpre = torch.empty((B * n_q, f1w.shape[0]), device=dev, dtype=act)
-        hact = _lin_fwd(on, f1w, f1b, wc, act, aux=hpre, epi=EPI_GELU)
-        x1 = _lin_fwd(hact, f2w, f2b, wc, torch.float32, resid=x)                       # :266
-        h, bsaved = x1, []
-        for l in range(cfg.depth):
-            h, s = block_fwd(h, blocks[12 * l:12 * l + 12], wc, heads, eps, act, B, n_q, save, dp=dp_of(l), drop=(p_attn, p_drop))   # :271
-            bsaved.append(s)
+        h, xsaved = queries, None                    # use_xattn=False (output_adapters.py:264-268): x = queries
+        if xattn:
+            qn, qmean, qrstd = ops.layernorm_fwd(queries, qnw, qnb, eps, act)
+            cn, cmean, crstd = ops.layernorm_fwd(context, cnw, cnb, eps, act)
+            q = _lin_fwd(qn, qw, qb, wc, act)
+            kv = _lin_fwd(cn, kvw, kvb, wc, act)
+            hd = D // heads
+            xo = torch.empty((B * n_q, D), device=dev, dtype=act)
+            Pm = ops.attention_fwd(AttnView(q, 0, D, n_q), AttnView(kv, 0, 2 * D, NC), AttnView(kv, D, 2 * D, NC),
+                                   AttnView(xo, 0, D, n_q), B, heads, hd, hd ** -0.5, drop_p=p_attn)
+            x = _lin_fwd(xo, pw_, pb, wc, torch.float32)                                    # :265, no residual
+            k_x = None
+            if p_drop > 0.:                                                                 # CrossAttention.proj_drop (multimae_utils.py:213)
+                k_x = ops._dropout_keep((B * n_q, D), p_drop, dev)
+                x = ops.dropout_apply(x, k_x, 1.0 / (1.0 - p_drop), out=x)
+            on, omean, orstd = ops.layernorm_fwd(x, onw, onb, eps, act)
+            hpre = torch.empty((B * n_q, f1w.shape[0]), device=dev, dtype=act)
+            hact = _lin_fwd(on, f1w, f1b, wc, act, aux=hpre, epi=EPI_GELU)
+            h = _lin_fwd(hact, f2w, f2b, wc, torch.float32, resid=x)                        # :266
+            xsaved = (queries, context, qn, qmean, qrstd, cn, cmean, crstd, q, kv, Pm, xo, x, on, omean, orstd, hpre, hact, k_x)
+        h, bsaved, _ = blocks_fwd(h, blocks, wc, heads, eps, act, B, n_q, save, dps, None if drops is None else [drops] * cfg.depth)   # :271
         h_act = ops.cast(h, act)
         pat = _lin_fwd(h_act, ow, ob, wc, torch.float32)                                # :274
         img = ops.unpatchify(pat, B, cfg.C, cfg.nh, cfg.nw, cfg.ph, cfg.pw)             # :277-280
         if save:
-            ctx.saved = (enc_act, queries, context, qn, qmean, qrstd, cn, cmean, crstd, q, kv, Pm, xo, x, on, omean, orstd,
-                         hpre, hact, h_act, bsaved, k_x)
-        ctx.cfg, ctx.params, ctx.ids = cfg, params, (ids_keep, ids_restore)
-        ctx.dims = (B, NC, Denc, n_keep, n_q, T)
+            ctx.saved = (enc_act, context.shape, xsaved, h_act, bsaved)
         return img
 
     @staticmethod
@@ -814,10 +842,8 @@ class SpatialAdapterFn(torch.autograd.Function):
         B, NC, Denc, n_keep, n_q, T = ctx.dims
         act, wc, D, G, heads = cfg.act, cfg.wc, cfg.D, cfg.G, cfg.heads
         lnact = None if act == torch.float32 else act
-        if getattr(ctx, 'comp', None) is not None:
-            sink = GradSink(engine.direct_grads())
-            dsts, acc = _grad_targets(sink, params)
-            use_side = sink.side is not None and acc
+        sink = GradSink(engine.direct_grads())
+        if ctx.comp is not None:
             h = getattr(ctx, 'handle', None)
             d_pat = h.d_pat if h is not None else None
             dy_amax = h.dy_amax if (h is not None and d_pat is not None and d_img is None) else None
@@ -825,121 +851,88 @@ class SpatialAdapterFn(torch.autograd.Function):
                 if d_img is not None:
                     raise NotImplementedError('this prediction received gradient both through a patch-domain loss and through the image '
                                               'tensor; turn the patch-domain losses off (engine.set_patch_domain_loss(False))')
-                d_pat.record_stream(torch.cuda.current_stream())     # produced by the loss's backward on another stream
+                if d_pat.is_cuda:
+                    d_pat.record_stream(torch.cuda.current_stream())     # produced by the loss's backward on another stream
                 h.d_pat, h.pat = None, None
             elif d_img is None:                                      # nothing reached this adapter
                 d_img = torch.zeros((B, cfg.C, cfg.nh * cfg.ph, cfg.nw * cfg.pw), device=params[0].device, dtype=torch.float32)
-            if getattr(ctx, 'h16', False) and (d_pat is None or d_pat.dtype != torch.float16):
+            if ctx.h16 and (d_pat is None or d_pat.dtype != torch.float16):
                 # the gradient did not come from a loss kernel that writes scaled fp16 rows (image-domain gradient, a pixel loss,
                 # several losses added up): bring it into the adapter's units here -- rows, their largest element, one scaled cast
                 rows = d_pat if d_pat is not None else ops.patchify(d_img.contiguous().float(), cfg.C, cfg.nh, cfg.nw, cfg.ph, cfg.pw, torch.float32)
                 dy_amax = rows.detach().abs().amax().reshape(1).float()
                 d_pat, d_img = ops.cast_f16(rows, scale_amax=dy_amax), None
-            lib_acc = acc and not engine.claim_first_write(params)      # first write since zero_grad(): store, do not accumulate
-            d_enc, keep = ops.adapter_bwd(ctx.comp, d_img, d_pat, [None if t is None else t.view(-1) for t in dsts], lib_acc,
-                                          sink.side.cuda_stream if use_side else None, dy_amax=dy_amax)
+            (d_enc,), grads, acc = _composite_bwd(sink, params, lambda dsts, acc, grad_acc, side: ops.adapter_bwd(
+                ctx.comp, d_img, d_pat, [None if t is None else t.view(-1) for t in dsts], grad_acc, side, dy_amax=dy_amax))
             ctx.comp = None
-            if use_side:
-                engine.mark_side_dirty(sink.side)
-                engine.keep_until_join(keep)
             if cfg.on_done is not None and acc:
                 cfg.on_done()
-            return (None, d_enc, None, None, *([None] * len(params) if acc else dsts))
-        xattn = bool(getattr(cfg, 'use_xattn', True))
-        if xattn:
-            (enc_act, queries, context, qn, qmean, qrstd, cn, cmean, crstd, q, kv, Pm, xo, x, on, omean, orstd, hpre, hact, h_act,
-             bsaved, k_x) = ctx.saved
-        else:
-            enc_act, ctx_shape, h_act, bsaved = ctx.saved
+            return (None, d_enc, None, None, *grads)
+        enc_act, ctx_shape, xsaved, h_act, bsaved = ctx.saved
+        ctx.saved = None
         if d_img is None:
             d_img = torch.zeros((B, cfg.C, cfg.nh * cfg.ph, cfg.nw * cfg.pw), device=params[0].device, dtype=torch.float32)
-        mask_token = params[0]
-        temb = params[1:1 + T]
-        (qw, qb, kvw, kvb, pw_, pb, cnw, cnb, qnw, qnb, onw, onb, f1w, f1b, f2w, f2b) = params[1 + T:17 + T]
-        blocks = params[17 + T:17 + T + 12 * cfg.depth]
-        ow, ob, pcw, pcb = params[17 + T + 12 * cfg.depth:]
+        (mask_token, temb, qw, qb, kvw, kvb, pw_, pb, cnw, cnb, qnw, qnb, onw, onb, f1w, f1b, f2w, f2b, blocks, ow, ob, pcw,
+         pcb) = _adapter_params(params, T, cfg.depth)
         dev = d_img.device
-        sink = GradSink(engine.direct_grads())
         hd = D // heads
 
         d_pat = ops.patchify(d_img, cfg.C, cfg.nh, cfg.nw, cfg.ph, cfg.pw, act)         # [B*n_q, C*ph*pw]
         g_ow, g_ob = sink.linear(ow, ob, d_pat, h_act)
         dh_act = ops.linear_dx(d_pat, wc(ow), torch.empty((B * n_q, D), device=dev, dtype=act))
         dh = ops.cast(dh_act, torch.float32)
-        bgrads: List[Optional[Tensor]] = [None] * (12 * cfg.depth)
-        fc2b_done, g_cs = False, None
-        dps = getattr(cfg, 'dp', None)
         drops = getattr(cfg, 'drops', None)
-        for l in reversed(range(cfg.depth)):
-            cs_param = blocks[12 * (l - 1) + 11] if l > 0 else (f2b if xattn else None)
-            if dps is not None and l > 0 and dps[2 * (l - 1) + 1] is not None:
-                cs_param = None                      # the block below rescales its MLP branch: colsum(dx0) is not its fc2 bias gradient
-            if l > 0 and drops is not None and drops[1] > 0.:
-                cs_param = None                      # ... or drops elements of its fc2 output
-            dh, dh_act, g_cs_next, g = block_bwd(dh, dh_act, fc2b_done, bsaved[l], blocks[12 * l:12 * l + 12], wc, sink, heads, act, B,
-                                                 n_q, cs_param, dp=(dps[2 * l], dps[2 * l + 1]) if dps is not None else (None, None))
-            bgrads[12 * l:12 * l + 12] = g
-            if fc2b_done:
-                bgrads[12 * l + 11] = g_cs
-            fc2b_done, g_cs = (cs_param is not None and cs_param.requires_grad), g_cs_next
-        if not xattn:                                # the queries fed the blocks directly: no cross-attention / MLP parameters
-            d_ctx, part_b = ops.decoder_build_bwd(dh, torch.zeros(ctx_shape, device=dev, dtype=torch.float32), ids_keep, ids_restore,
-                                                  cfg.task_offsets, cfg.q_task, B, n_keep, G, D, n_q, raw=True)
-            g_build = sink.colsums(part_b, D, list(temb) + [mask_token])
-            d_ctx_act = ops.cast(d_ctx, act)
-            g_pcw, g_pcb = sink.linear(pcw, pcb, d_ctx_act, enc_act)
-            d_enc = ops.linear_dx(d_ctx_act, wc(pcw), torch.empty((B * NC, Denc), device=dev, dtype=torch.float32))
-            ctx.saved = None
-            if cfg.on_done is not None and all(x is None for x in (g_build[T], *g_build[:T], *bgrads, g_ow, g_ob, g_pcw, g_pcb)):
-                cfg.on_done()
-            return (None, d_enc.view(B, NC, Denc), None, None, g_build[T], *g_build[:T], *([None] * 16), *bgrads, g_ow, g_ob, g_pcw, g_pcb)
-        # x1 = x + mlp(out_norm(x))
-        Hd = f1w.shape[0]
-        part_h = torch.empty(ops.dx_colsum_part_shape(B * n_q, Hd), device=dev, dtype=torch.float32)
-        d_hpre = ops.linear_dx(dh_act, wc(f2w), torch.empty(hpre.shape, device=dev, dtype=act), aux=hpre, epi=EPI_DGELU, colsum_part=part_h)
-        if fc2b_done:
-            g_f2w, g_f2b = sink.weight(f2w, dh_act, hact), g_cs
+        # with cross attention the blocks' input came out of this adapter's own MLP: its fc2.bias rides on block 0's reduction
+        dh, dh_act, bgrads, fc2b_done, g_cs = blocks_bwd(dh, dh_act, bsaved, blocks, wc, sink, heads, act, B, n_q, getattr(cfg, 'dp', None),
+                                                         None if drops is None else [drops] * cfg.depth, below=f2b if xsaved is not None else None)
+        if xsaved is None:                           # the queries fed the blocks directly: no cross-attention / MLP parameters
+            d_queries, d_context = dh, torch.zeros(ctx_shape, device=dev, dtype=torch.float32)
+            xgrads = [None] * 16
         else:
-            g_f2w, g_f2b = sink.linear(f2w, f2b, dh_act, hact)
-        d_on = ops.linear_dx(d_hpre, wc(f1w), torch.empty((B * n_q, D), device=dev, dtype=act))
-        g_f1w, g_f1b = sink.weight(f1w, d_hpre, on), sink.colsums(part_h, Hd, [f1b])[0]
-        dx, dx_act, part_o = ops.layernorm_bwd_part(d_on, x, onw, omean, orstd, dh, lnact)
-        if dx_act is None:
-            dx_act = dx
-        # x = proj_drop(proj(attn(q, k, v)))
-        if k_x is None:
-            g_onw, g_onb, g_pb = sink.colsums(part_o, D, [onw, onb, pb])
-            g_pw = sink.weight(pw_, dx_act, xo)
-        else:                                        # the bias gradient is the column sums of the gradient BEHIND the dropout
-            g_onw, g_onb, _ = sink.colsums(part_o, D, [onw, onb, None])
-            dx_act = ops.dropout_apply(dx, k_x, 1.0 / (1.0 - drops[1]), out_dtype=act)
-            g_pw, g_pb = sink.linear(pw_, pb, dx_act, xo)
-        d_xo = ops.linear_dx(dx_act, wc(pw_), torch.empty((B * n_q, D), device=dev, dtype=act))
-        d_q = torch.empty((B * n_q, D), device=dev, dtype=act)
-        d_kv = torch.empty((B * NC, 2 * D), device=dev, dtype=act)
-        ops.attention_bwd(AttnView(q, 0, D, n_q), AttnView(kv, 0, 2 * D, NC), AttnView(kv, D, 2 * D, NC), Pm,
-                          AttnView(xo, 0, D, n_q), AttnView(d_xo, 0, D, n_q), AttnView(d_q, 0, D, n_q), AttnView(d_kv, 0, 2 * D, NC),
-                          AttnView(d_kv, D, 2 * D, NC), B, heads, hd, hd ** -0.5)
-        d_qn = ops.linear_dx(d_q, wc(qw), torch.empty((B * n_q, D), device=dev, dtype=act))
-        g_qw, g_qb = sink.linear(qw, qb, d_q, qn)
-        d_cn = ops.linear_dx(d_kv, wc(kvw), torch.empty((B * NC, D), device=dev, dtype=act))
-        g_kvw, g_kvb = sink.linear(kvw, kvb, d_kv, cn)
-        d_queries, _, part_q = ops.layernorm_bwd_part(d_qn, queries, qnw, qmean, qrstd, None, None)
-        g_qnw, g_qnb, _ = sink.colsums(part_q, D, [qnw, qnb, None])
-        d_context, _, part_c = ops.layernorm_bwd_part(d_cn, context, cnw, cmean, crstd, None, None)
-        g_cnw, g_cnb, _ = sink.colsums(part_c, D, [cnw, cnb, None])
+            queries, context, qn, qmean, qrstd, cn, cmean, crstd, q, kv, Pm, xo, x, on, omean, orstd, hpre, hact, k_x = xsaved
+            # x1 = x + mlp(out_norm(x))
+            Hd = f1w.shape[0]
+            part_h = torch.empty(ops.dx_colsum_part_shape(B * n_q, Hd), device=dev, dtype=torch.float32)
+            d_hpre = ops.linear_dx(dh_act, wc(f2w), torch.empty(hpre.shape, device=dev, dtype=act), aux=hpre, epi=EPI_DGELU, colsum_part=part_h)
+            if fc2b_done:
+                g_f2w, g_f2b = sink.weight(f2w, dh_act, hact), g_cs
+            else:
+                g_f2w, g_f2b = sink.linear(f2w, f2b, dh_act, hact)
+            d_on = ops.linear_dx(d_hpre, wc(f1w), torch.empty((B * n_q, D), device=dev, dtype=act))
+            g_f1w, g_f1b = sink.weight(f1w, d_hpre, on), sink.colsums(part_h, Hd, [f1b])[0]
+            dx, dx_act, part_o = ops.layernorm_bwd_part(d_on, x, onw, omean, orstd, dh, lnact)
+            if dx_act is None:
+                dx_act = dx
+            # x = proj_drop(proj(attn(q, k, v)))
+            if k_x is None:
+                g_onw, g_onb, g_pb = sink.colsums(part_o, D, [onw, onb, pb])
+                g_pw = sink.weight(pw_, dx_act, xo)
+            else:                                        # the bias gradient is the column sums of the gradient BEHIND the dropout
+                g_onw, g_onb, _ = sink.colsums(part_o, D, [onw, onb, None])
+                dx_act = ops.dropout_apply(dx, k_x, 1.0 / (1.0 - drops[1]), out_dtype=act)
+                g_pw, g_pb = sink.linear(pw_, pb, dx_act, xo)
+            d_xo = ops.linear_dx(dx_act, wc(pw_), torch.empty((B * n_q, D), device=dev, dtype=act))
+            d_q = torch.empty((B * n_q, D), device=dev, dtype=act)
+            d_kv = torch.empty((B * NC, 2 * D), device=dev, dtype=act)
+            ops.attention_bwd(AttnView(q, 0, D, n_q), AttnView(kv, 0, 2 * D, NC), AttnView(kv, D, 2 * D, NC), Pm,
+                              AttnView(xo, 0, D, n_q), AttnView(d_xo, 0, D, n_q), AttnView(d_q, 0, D, n_q), AttnView(d_kv, 0, 2 * D, NC),
+                              AttnView(d_kv, D, 2 * D, NC), B, heads, hd, hd ** -0.5)
+            d_qn = ops.linear_dx(d_q, wc(qw), torch.empty((B * n_q, D), device=dev, dtype=act))
+            g_qw, g_qb = sink.linear(qw, qb, d_q, qn)
+            d_cn = ops.linear_dx(d_kv, wc(kvw), torch.empty((B * NC, D), device=dev, dtype=act))
+            g_kvw, g_kvb = sink.linear(kvw, kvb, d_kv, cn)
+            d_queries, _, part_q = ops.layernorm_bwd_part(d_qn, queries, qnw, qmean, qrstd, None, None)
+            g_qnw, g_qnb, _ = sink.colsums(part_q, D, [qnw, qnb, None])
+            d_context, _, part_c = ops.layernorm_bwd_part(d_cn, context, cnw, cmean, crstd, None, None)
+            g_cnw, g_cnb, _ = sink.colsums(part_c, D, [cnw, cnb, None])
+            xgrads = [g_qw, g_qb, g_kvw, g_kvb, g_pw, g_pb, g_cnw, g_cnb, g_qnw, g_qnb, g_onw, g_onb, g_f1w, g_f1b, g_f2w, g_f2b]
         d_ctx, part_b = ops.decoder_build_bwd(d_queries, d_context, ids_keep, ids_restore, cfg.task_offsets, cfg.q_task, B, n_keep, G, D,
                                               n_q, raw=True)
         g_build = sink.colsums(part_b, D, list(temb) + [mask_token])
         d_ctx_act = ops.cast(d_ctx, act)
         g_pcw, g_pcb = sink.linear(pcw, pcb, d_ctx_act, enc_act)
         d_enc = ops.linear_dx(d_ctx_act, wc(pcw), torch.empty((B * NC, Denc), device=dev, dtype=torch.float32))
-        g_mask = g_build[T]
-        g_temb = g_build[:T]
-        ctx.saved = None
-        grads = [g_mask, *g_temb, g_qw, g_qb, g_kvw, g_kvb, g_pw, g_pb, g_cnw, g_cnb,
-                 g_qnw, g_qnb, g_onw, g_onb, g_f1w, g_f1b, g_f2w, g_f2b,
-                 *bgrads, g_ow, g_ob, g_pcw, g_pcb]
+        grads = [g_build[T], *g_build[:T], *xgrads, *bgrads, g_ow, g_ob, g_pcw, g_pcb]      # mask_token, task embeddings, ...
         if cfg.on_done is not None and all(x is None for x in grads):
             cfg.on_done()
         return (None, d_enc.view(B, NC, Denc), None, None, *grads)
@@ -1327,15 +1320,7 @@ class ConvNeXtHeadFn(torch.autograd.Function):
         geom = (B, h, w, K, H, W, cfg.mode)
         if engine.lazy_predictions() and engine.capturing() is None:
             # the image is an API output the fused loss and argmax never read (criterion.SegCrossEntropyLoss, metrics.seg_argmax)
-            ev = torch.cuda.current_stream().record_event() if enc.is_cuda else None
-
-            def fill(dst, logits=logits, ev=ev, geom=geom, Kp=Kp):
-                if ev is not None:
-                    cur = torch.cuda.current_stream()
-                    cur.wait_event(ev)
-                    logits.record_stream(cur)
-                ops.resize_fwd(logits, Kp, dst, *geom)
-            cfg.lazy_fill = fill
+            cfg.lazy_fill = _lazy_image(logits, lambda logits, dst: ops.resize_fwd(logits, Kp, dst, *geom))
         else:
             ops.resize_fwd(logits, Kp, out, *geom)                # F.interpolate (:568)
         token = out.new_empty(1)

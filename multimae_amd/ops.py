@@ -378,6 +378,21 @@ def stream_workspace(stream_handle: int, device, elems: Optional[int] = None) ->
     return w
 
 
+def _bind_ws(d, device, side_handle: Optional[int] = None, *, bwd: bool = False):
+    """The stream workspaces of a composite call into its descriptor `d`; returns the (compute, side) stream handles of the call.
+    A forward binds ws_main only.  A backward (bwd) also binds ws_side: the side stream's own workspace, or ws_main again when
+    there is no side stream (side_handle None) or it is the compute stream itself -- one stream, one workspace."""
+    st = _stream()
+    wm = stream_workspace(st, device)
+    d.ws_main, d.ws_main_elems = wm.data_ptr(), wm.numel()
+    if not bwd:
+        return st, None
+    sd = side_handle if side_handle is not None else st
+    wsd = stream_workspace(sd, device) if sd != st else wm
+    d.ws_side, d.ws_side_elems = wsd.data_ptr(), wsd.numel()
+    return st, sd
+
+
 LDS_BYTES = 160 * 1024                                    # LDS of one compute unit (csrc/common.h: MMAE_LDS_BYTES)
 
 
@@ -424,9 +439,7 @@ def block_fwd_composite(x: Tensor, P: Sequence[Tensor], wts: Sequence[Tensor], h
     d.x0, d.ln1, d.mean1, d.rstd1, d.qkv, d.lse, d.ao, d.x1 = (x.data_ptr(), ln1.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
                                                                qkv.data_ptr(), lse.data_ptr(), ao.data_ptr(), x1.data_ptr())
     d.ln2, d.mean2, d.rstd2, d.hpre, d.hact, d.x2 = ln2.data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), hpre.data_ptr(), hact.data_ptr(), x2.data_ptr()
-    st = _stream()
-    ws = stream_workspace(st, dev)
-    d.ws_main, d.ws_main_elems = ws.data_ptr(), ws.numel()
+    st, _ = _bind_ws(d, dev)
     check(_lib.load().mmae_block_fwd(ctypes.byref(d), st), 'block_fwd')
     # third entry: `hpre` holds GELU'(pre-activation) (bf16 activations, mmae_gelu_grad_aux on) instead of the pre-activation
     hpre_is_grad = act == torch.bfloat16 and bool(_lib.load().mmae_gelu_grad_aux(-1))
@@ -466,12 +479,7 @@ def block_bwd_composite(dx: Tensor, dx_act: Tensor, fc2b_done: bool, saved, P: S
      d.g_fc2_b) = (_p(g) for g in grads)
     d.g_cs = _p(g_cs)
     d.grad_acc, d.fc2_b_done = int(grad_acc), int(fc2b_done)
-    st = _stream()
-    wm = stream_workspace(st, dev)
-    d.ws_main, d.ws_main_elems = wm.data_ptr(), wm.numel()
-    sd = side_handle if side_handle is not None else st
-    wsd = stream_workspace(sd, dev) if sd != st else wm
-    d.ws_side, d.ws_side_elems = wsd.data_ptr(), wsd.numel()
+    st, sd = _bind_ws(d, dev, side_handle, bwd=True)
     check(lib.mmae_block_bwd(ctypes.byref(d), st, sd), 'block_bwd')
     keep = (d_hpre, d_ln2, d_ao, d_qkv, d_ln1, dx1, dx1_act, part, dx, dx_act, saved)
     return dx0, (dx0_act if bf else dx0), keep
@@ -497,8 +505,9 @@ def _ptr_arr(ptrs: Sequence[Optional[int]]):
 
 
 class _PtrCache:
-    """ctypes pointer tables of a parameter list, rebuilt only when a watched address changes (the arena views and their
-    bf16 shadows never move; stand-alone modules re-cast their weights every forward and simply miss)."""
+    """What the host derives from a parameter list -- ctypes pointer tables (_PTRS), device copy sets of the weights (_SHADOWS) --
+    rebuilt only when a watched address changes (the arena views and their bf16 shadows never move; stand-alone modules re-cast
+    their weights every forward and simply miss)."""
 
     def __init__(self):
         self.tabs = {}
@@ -530,10 +539,9 @@ class MxStackWeights:
     """MX-fp8 copies of the four Linear weights of every block of a stack (both orientations, mmae_mx_prepare_weights): one
     byte buffer + the host pointer table mmae_stack_desc.mx_w wants.  refresh() re-quantises from the f32 master weights."""
 
-    def __init__(self, params: Sequence[Tensor]):
+    def __init__(self, ws: Sequence[Tensor]):
         lib = _lib.load()
-        L = len(params) // 12
-        self.ws = [params[12 * l + i] for l in range(L) for i in (2, 4, 8, 10)]
+        self.ws = list(ws)
         dev = self.ws[0].device
         offs, total = [], 0
         for w in self.ws:
@@ -547,47 +555,46 @@ class MxStackWeights:
         self.src = _ptr_arr([w.data_ptr() for w in self.ws])
         self.n_out = (ctypes.c_int32 * len(self.ws))(*[w.shape[0] for w in self.ws])
         self.k_in = (ctypes.c_int32 * len(self.ws))(*[w.shape[1] for w in self.ws])
-        self.probe = tuple(w.data_ptr() for w in self.ws[:1] + self.ws[-1:])
-        self.shapes = tuple(tuple(w.shape) for w in self.ws)
-
-    def matches(self, params: Sequence[Tensor]) -> bool:
-        if self.probe != (params[2].data_ptr(), params[-2].data_ptr()) or len(self.ws) * 3 != len(params):
-            return False
-        L = len(params) // 12
-        return self.shapes == tuple(tuple(params[12 * l + i].shape) for l in range(L) for i in (2, 4, 8, 10))
 
     def refresh(self) -> None:
         check(_lib.load().mmae_mx_prepare_weights(len(self.ws), ctypes.cast(self.src, ctypes.c_void_p), F32, self.n_out, self.k_in,
                                                   ctypes.cast(self.dst, ctypes.c_void_p), _stream()), 'mmae_mx_prepare_weights')
 
 
-_MX_STACKS = {}
+_SHADOWS = _PtrCache()
 
 
-def mx_stack_weights(params: Sequence[Tensor]) -> MxStackWeights:
-    key = (id(params[2]), len(params))
-    m = _MX_STACKS.get(key)
-    if m is None or not m.matches(params):
-        if len(_MX_STACKS) > 8:
-            _MX_STACKS.clear()
-        m = MxStackWeights(params)
-        _MX_STACKS[key] = m
-    return m
+def _weight_shadow(cls, ws: Sequence[Tensor]):
+    """The `cls` copy set (MxStackWeights, X3Weights, H16Weights) of the f32 weights `ws`, built once per set of weights.  Keyed by where
+    the first weight LIVES -- the callers hand in fresh detach() views every forward, their id() is not stable (a key on id() allocated
+    a new copy set every step) -- and valid while every weight is where, and of the shape, it was."""
+    return _SHADOWS.get((cls, ws[0].data_ptr(), len(ws)), tuple((w.data_ptr(), w.shape) for w in ws), lambda: cls(ws))
+
+
+def mx_stack_weights(ws: Sequence[Tensor]) -> MxStackWeights:
+    """ws: qkv, proj, fc1, fc2 weight of every block, in block order"""
+    return _weight_shadow(MxStackWeights, ws)
 
 
 def mx_stack_ok(D: int, Hd: int, act: torch.dtype) -> bool:
     return act == torch.bfloat16 and D % 256 == 0 and Hd % 256 == 0
 
 
-def _stack_tables(params: Sequence[Tensor], wc, L: int, act: torch.dtype):
-    """(act-dtype weights, mmae_stack_desc.w, mmae_stack_desc.p) of a stack: the pointer tables cached per parameter list, shared by
-    stack_fwd and stack_fwd_infer"""
+def _stack_desc(x: Tensor, params: Sequence[Tensor], wc, heads: int, eps: float, act: torch.dtype, B: int, N: int):
+    """mmae_stack_desc of L = len(params) // 12 blocks on x f32 [B*N, D]: geometry, dtypes, input and the host pointer tables (cached
+    per parameter list).  Returns (descriptor, what must stay alive with it: the two tables and the act-dtype weights)."""
+    L = len(params) // 12
+    d = StackDesc()
+    d.L, d.B, d.N, d.D, d.heads, d.Hd = L, B, N, x.shape[1], heads, params[8].shape[0]
+    d.act_dtype, d.f32_gemm, d.eps = dcode(act), _f32_code(), eps
     wts = [wc(params[12 * l + i]) for l in range(L) for i in (2, 4, 8, 10)]
     probe = (wts[0].data_ptr(), wts[-1].data_ptr(), params[0].data_ptr(), params[-1].data_ptr())
     w_arr, p_arr = _PTRS.get(('stack', id(params[0]), L, act), probe, lambda: (
         _ptr_arr([w.data_ptr() for w in wts]),
         _ptr_arr([params[12 * l + i].data_ptr() for l in range(L) for i in (0, 1, 3, 5, 6, 7, 9, 11)])))
-    return wts, w_arr, p_arr
+    d.w, d.p = ctypes.cast(w_arr, ctypes.c_void_p), ctypes.cast(p_arr, ctypes.c_void_p)
+    d.x = x.data_ptr()
+    return d, (w_arr, p_arr, wts)
 
 
 def stack_fwd(x: Tensor, params: Sequence[Tensor], wc, heads: int, eps: float, act: torch.dtype, B: int, N: int,
@@ -598,37 +605,30 @@ def stack_fwd(x: Tensor, params: Sequence[Tensor], wc, heads: int, eps: float, a
     call also runs the weight gradients on them (mx_wgrad)."""
     lib = _lib.load()
     R, D = x.shape
-    L = len(params) // 12
-    Hd = params[8].shape[0]
-    d = StackDesc()
-    d.L, d.B, d.N, d.D, d.heads, d.Hd = L, B, N, D, heads, Hd
-    d.act_dtype, d.f32_gemm, d.eps = dcode(act), _f32_code(), eps
-    wts, w_arr, p_arr = _stack_tables(params, wc, L, act)
-    d.w, d.p = ctypes.cast(w_arr, ctypes.c_void_p), ctypes.cast(p_arr, ctypes.c_void_p)
+    d, tables = _stack_desc(x, params, wc, heads, eps, act, B, N)
+    L, Hd = d.L, d.Hd
     dp_arr = None
     if dp is not None and any(t is not None for t in dp):
         dp_arr = _ptr_arr([_p(t) for t in dp])
         d.dp = ctypes.cast(dp_arr, ctypes.c_void_p)
-    d.x = x.data_ptr()
     mxw = None
     if mx and mx_stack_ok(D, Hd, act):
-        assert all(params[12 * l + i].dtype == torch.float32 for l in range(L) for i in (2, 4, 8, 10))
-        mxw = mx_stack_weights(params)
+        masters = [params[12 * l + i] for l in range(L) for i in (2, 4, 8, 10)]
+        assert all(w.dtype == torch.float32 for w in masters)
+        mxw = mx_stack_weights(masters)
         mxw.refresh()
         d.mx_w = ctypes.cast(mxw.dst, ctypes.c_void_p)
     nbytes = lib.mmae_stack_act_bytes(ctypes.byref(d))
     slab = _slab(nbytes, x.device)
     d.act, d.act_bytes = slab.data_ptr(), slab.numel()
-    st = _stream()
-    ws = stream_workspace(st, x.device)
-    d.ws_main, d.ws_main_elems = ws.data_ptr(), ws.numel()
+    st, _ = _bind_ws(d, x.device)
     check(lib.mmae_stack_fwd(ctypes.byref(d), st), 'stack_fwd')
     outs = []
     for l in range(L):
         off = lib.mmae_stack_out_offset(ctypes.byref(d), l)
         outs.append(slab[off:off + R * D * 4].view(torch.float32).view(R, D))
     s = StackState()
-    s.desc, s.act, s.keep, s.x, s.L, s.shape, s.act_dtype, s.dp = d, slab, (w_arr, p_arr, dp_arr, wts, dp, mxw), x, L, (B, N, D, Hd), act, dp
+    s.desc, s.act, s.keep, s.x, s.L, s.shape, s.act_dtype, s.dp = d, slab, (*tables, dp_arr, dp, mxw), x, L, (B, N, D, Hd), act, dp
     return outs, s
 
 
@@ -641,25 +641,17 @@ def stack_fwd_infer(x: Tensor, params: Sequence[Tensor], wc, heads: int, eps: fl
     temporary."""
     lib = _lib.load()
     R, D = x.shape
-    L = len(params) // 12
-    Hd = params[8].shape[0]
-    d = StackDesc()
-    d.L, d.B, d.N, d.D, d.heads, d.Hd = L, B, N, D, heads, Hd
-    d.act_dtype, d.f32_gemm, d.eps = dcode(act), _f32_code(), eps
-    wts, w_arr, p_arr = _stack_tables(params, wc, L, act)
-    d.w, d.p = ctypes.cast(w_arr, ctypes.c_void_p), ctypes.cast(p_arr, ctypes.c_void_p)
-    d.x = x.data_ptr()
+    d, tables = _stack_desc(x, params, wc, heads, eps, act, B, N)
+    L = d.L
     kept = set(range(L)) if keep == 'all_layers' else ({L - 1} if keep == 'last' else {int(l) for l in keep} | {L - 1})
     assert all(0 <= l < L for l in kept), kept
     outs = {l: torch.empty((R, D), device=x.device, dtype=torch.float32) for l in sorted(kept)}
     o_arr = _ptr_arr([outs[l].data_ptr() if l in outs else None for l in range(L)])
     slab = _slab(lib.mmae_stack_infer_bytes(ctypes.byref(d)), x.device)
     d.act, d.act_bytes = slab.data_ptr(), slab.numel()
-    st = _stream()
-    ws = stream_workspace(st, x.device)
-    d.ws_main, d.ws_main_elems = ws.data_ptr(), ws.numel()
+    st, _ = _bind_ws(d, x.device)
     check(lib.mmae_stack_fwd_infer(ctypes.byref(d), ctypes.cast(o_arr, ctypes.c_void_p), st), 'stack_fwd_infer')
-    del wts                                               # (alive until here: the call reads the act-dtype weights)
+    del tables                                            # (alive until here: the call reads the act-dtype weights)
     return [outs[l] for l in sorted(kept)]
 
 
@@ -683,12 +675,7 @@ def stack_bwd(s: StackState, d_outs: Sequence[Optional[Tensor]], grads: Sequence
     d.dx = dx.data_ptr()
     tmp = _slab(lib.mmae_stack_tmp_bytes(ctypes.byref(d)), dev)
     d.tmp, d.tmp_bytes = tmp.data_ptr(), tmp.numel()
-    st = _stream()
-    wm = stream_workspace(st, dev)
-    d.ws_main, d.ws_main_elems = wm.data_ptr(), wm.numel()
-    sd = side_handle if side_handle is not None else st
-    wsd = stream_workspace(sd, dev) if sd != st else wm
-    d.ws_side, d.ws_side_elems = wsd.data_ptr(), wsd.numel()
+    st, sd = _bind_ws(d, dev, side_handle, bwd=True)
     for lo, hi in (chunks or [(0, s.L)]):
         d.l_begin, d.l_end = lo, hi
         check(lib.mmae_stack_bwd(ctypes.byref(d), st, sd), 'stack_bwd')
@@ -703,7 +690,7 @@ class AdapterState:
 
 def adapter_composite_ok(enc: Tensor, act: torch.dtype, heads: int, D: int, n_q: int, NC: int, depth: int, T: int, KP: int) -> bool:
     hd = D // heads
-    if not (_STACK[0] and _ADAPTER[0] and _COMPOSITE[0] and _FUSED_ATTN[0] and enc.is_cuda and hd in (32, 64) and n_q <= 256 and NC <= 256 and depth <= 8
+    if not (_STACK[0] and _ADAPTER[0] and _COMPOSITE[0] and _FUSED_ATTN[0] and _device_ok(enc) and hd in (32, 64) and n_q <= 256 and NC <= 256 and depth <= 8
             and T <= 7 and D % 8 == 0 and enc.shape[-1] % 8 == 0 and KP % 4 == 0):
         return False
     if act == torch.bfloat16:
@@ -730,17 +717,12 @@ class X3Weights:
         self.n_out = (ctypes.c_int32 * len(self.ws))(*[w.shape[0] for w in self.ws])
         self.k_in = (ctypes.c_int32 * len(self.ws))(*[w.numel() // w.shape[0] for w in self.ws])
         self.triples = _ptr_arr([v for i, w in enumerate(self.ws) for v in (w.data_ptr(), base + offs[2 * i], base + offs[2 * i + 1])])
-        self.probe = tuple(w.data_ptr() for w in self.ws)
-
-    def matches(self, w_list: Sequence[Tensor]) -> bool:
-        return self.probe == tuple(w.data_ptr() for w in w_list)
 
     def refresh(self) -> None:
         check(_lib.load().mmae_x3_prepare_weights(len(self.ws), ctypes.cast(self.src, ctypes.c_void_p), self.n_out, self.k_in,
                                                   ctypes.cast(self.dst, ctypes.c_void_p), _stream()), 'mmae_x3_prepare_weights')
 
 
-_X3_SETS = {}
 # Off by default: measured +1.2 ms per cfg3 step (36.2 against 35.0 ms, profiles/r02_x3_presplit_ab.txt).  The fp32 adapter's products
 # have K = 256: as ONE bf16 product over 3 K on the persistent 256 x 256 ping-pong kernel they are prologue / f32-epilogue bound and
 # no faster than on the 128 x 128 kernel that splits in registers (three workgroups per CU hide each other's epilogues), and the
@@ -749,14 +731,7 @@ _X3_PRESPLIT = _os.environ.get('MMAE_X3_PRESPLIT', '0') == '1'
 
 
 def x3_weights(w_list: Sequence[Tensor]) -> X3Weights:
-    key = (id(w_list[0]), len(w_list))
-    m = _X3_SETS.get(key)
-    if m is None or not m.matches(w_list):
-        if len(_X3_SETS) > 16:
-            _X3_SETS.clear()
-        m = X3Weights(w_list)
-        _X3_SETS[key] = m
-    return m
+    return _weight_shadow(X3Weights, w_list)
 
 
 def adapter_fwd(enc: Tensor, enc_act: Optional[Tensor], ids_keep: Tensor, ids_restore: Tensor, cfg, w_list: Sequence[Tensor],
@@ -799,9 +774,7 @@ def adapter_fwd(enc: Tensor, enc_act: Optional[Tensor], ids_keep: Tensor, ids_re
     d.act, d.act_bytes = slab.data_ptr(), slab.numel()
     img = torch.empty((B, cfg.C, cfg.nh * cfg.ph, cfg.nw * cfg.pw), device=enc.device, dtype=torch.float32) if want_img else None
     d.img = _p(img)
-    st = _stream()
-    ws = stream_workspace(st, enc.device)
-    d.ws_main, d.ws_main_elems = ws.data_ptr(), ws.numel()
+    st, _ = _bind_ws(d, enc.device)
     check(lib.mmae_adapter_fwd(ctypes.byref(d), st), 'adapter_fwd')
     s = AdapterState()
     s.pat = pat
@@ -828,12 +801,7 @@ def adapter_bwd(s: AdapterState, d_img: Optional[Tensor], d_pat: Optional[Tensor
     d.d_enc = d_enc.data_ptr()
     tmp = _slab(lib.mmae_adapter_tmp_bytes(ctypes.byref(d)), dev)
     d.tmp, d.tmp_bytes = tmp.data_ptr(), tmp.numel()
-    st = _stream()
-    wm = stream_workspace(st, dev)
-    d.ws_main, d.ws_main_elems = wm.data_ptr(), wm.numel()
-    sd = side_handle if side_handle is not None else st
-    wsd = stream_workspace(sd, dev) if sd != st else wm
-    d.ws_side, d.ws_side_elems = wsd.data_ptr(), wsd.numel()
+    st, sd = _bind_ws(d, dev, side_handle, bwd=True)
     check(lib.mmae_adapter_bwd(ctypes.byref(d), st, sd), 'adapter_bwd')
     return d_enc, (tmp, s.act, s.keep, d_img, d_pat, g_arr, grads, dy_amax)
 
@@ -980,8 +948,7 @@ class H16Weights:
     def __init__(self, w_list: Sequence[Tensor]):
         self.ws = list(w_list)
         dev = self.ws[0].device
-        self.probe = tuple(w.data_ptr() for w in self.ws)
-        lo = min(self.probe)
+        lo = min(w.data_ptr() for w in self.ws)
         hi = max(w.data_ptr() + w.numel() * 4 for w in self.ws)
         total = sum(w.numel() for w in self.ws)
         same = all(w.dtype == torch.float32 and w.is_contiguous() and w.untyped_storage().data_ptr() == self.ws[0].untyped_storage().data_ptr()
@@ -995,9 +962,6 @@ class H16Weights:
         else:
             self.copies = [torch.empty(w.shape, device=dev, dtype=torch.float16) for w in self.ws]
 
-    def matches(self, w_list: Sequence[Tensor]) -> bool:
-        return self.probe == tuple(w.data_ptr() for w in w_list)
-
     def refresh(self) -> Sequence[Tensor]:
         if self.span:
             cast_f16(self.src, out=self.buf)
@@ -1007,19 +971,8 @@ class H16Weights:
         return self.copies
 
 
-_H16_SETS = {}
-
-
 def h16_weights(w_list: Sequence[Tensor]) -> H16Weights:
-    # keyed by where the first weight LIVES (the callers hand in fresh detach() views every forward: their id() is not stable)
-    key = (w_list[0].data_ptr(), len(w_list))
-    s = _H16_SETS.get(key)
-    if s is None or not s.matches(w_list):
-        if len(_H16_SETS) > 16:
-            _H16_SETS.clear()
-        s = H16Weights(w_list)
-        _H16_SETS[key] = s
-    return s
+    return _weight_shadow(H16Weights, w_list)
 
 
 def adapter_h16_ok(enc: Tensor, heads: int, D: int, Hd: int, n_q: int, NC: int, depth: int, T: int, KP: int) -> bool:

@@ -9,17 +9,9 @@ import pytest
 import torch
 
 import dryrun_harness
+from dryrun_harness import RecordingLib
 
 NEW = ('mmae_attn_fwd_tiled', 'mmae_attn_bwd_tiled')
-
-
-class RecordingLib(dryrun_harness.FakeLib):
-    def __init__(self):
-        self.__dict__['names'] = []
-
-    def __getattr__(self, name):
-        self.__dict__['names'].append(name)
-        return dryrun_harness.FakeLib.__getattr__(self, name)
 
 
 @pytest.fixture()

@@ -143,7 +143,7 @@ def test_mxfp8_mode_and_option_plumbing(stubbed):
     finally:
         ops._X3_PRESPLIT = old
         M.engine.set_direct_grads(False)
-        type(lib).__getattr__ = orig
+        type(lib).__getattr__ = orig.__func__                 # (the function, not the method bound to this one instance)
     assert calls.count('mmae_mx_prepare_weights') == 1 and calls.count('mmae_stack_fwd') == 1 and calls.count('mmae_stack_bwd') == 1, calls
     # constructor options that used to raise
     from multimae_amd.multimae_utils import Block, run_blocks
@@ -253,14 +253,18 @@ def test_dropout_control_flow(stubbed, mode):
         ops._dropout_keep = real
 
 
-def test_fp16_weight_copies_are_cached_by_storage_not_by_object():
-    """ops.h16_weights: the fp16 copies of an fp32 adapter's weights are allocated once per set of weights -- the callers pass fresh detach()
-    views every forward, so the cache must key on where the weights live (a key on id() allocated a new copy every step)."""
+def test_fp16_weight_copies_are_cached_by_storage_not_by_object(stubbed):
+    """ops.h16_weights, ops.x3_weights, ops.mx_stack_weights: the device copies of a set of f32 weights are allocated once per set of weights
+    -- the callers pass fresh detach() views every forward, so the cache must key on where the weights live (a key on id() allocated a new
+    copy set every step)."""
     from multimae_amd import ops
-    ws = [torch.nn.Parameter(torch.randn(8, 8)) for _ in range(3)]
-    a = ops.h16_weights([w.detach() for w in ws])
-    b = ops.h16_weights([w.detach() for w in ws])
-    assert a is b and len(a.copies) == 3 and a.copies[0].dtype == torch.float16
-    other = [torch.nn.Parameter(torch.randn(8, 8)) for _ in range(3)]
-    assert ops.h16_weights([w.detach() for w in other]) is not a
-    assert ops.h16_weights([w.detach() for w in ws]) is a
+    for cached in (ops.h16_weights, ops.x3_weights, ops.mx_stack_weights):
+        ws = [torch.nn.Parameter(torch.randn(8, 8)) for _ in range(3)]
+        a = cached([w.detach() for w in ws])
+        b = cached([w.detach() for w in ws])
+        assert a is b, cached.__name__
+        if cached is ops.h16_weights:
+            assert len(a.copies) == 3 and a.copies[0].dtype == torch.float16
+        other = [torch.nn.Parameter(torch.randn(8, 8)) for _ in range(3)]
+        assert cached([w.detach() for w in other]) is not a, cached.__name__
+        assert cached([w.detach() for w in ws]) is a, cached.__name__
