@@ -332,7 +332,28 @@ def random_erasing(args):
                            num_splits=0, device='cuda')
 
 
-def cls_staged_loader(data_loader, args, device=None, train=True, erase_float32=True):
+def rand_augment(args):
+    """Replaces the ``rand_augment_transform(auto_augment, aa_params)`` that ``transforms_imagenet_train`` builds from ``--aa``,
+    ``--input_size`` and ``--train_interpolation`` (utils/transforms_factory.py:86-99): the engine's ``multimae_amd.RandAugment``
+    with the same ``aa_params``, applied to the uint8 batch on the device (hand it to ``cls_staged_loader``), or None when ``--aa``
+    is off.  AutoAugment / AugMix configs raise ``NotImplementedError``: they stay on the host."""
+    from multimae_amd import staging
+    aa = getattr(args, 'aa', None)
+    if not aa or str(aa).lower() == 'none':
+        return None
+    img_size = getattr(args, 'input_size', 224)
+    img_size_min = min(img_size) if isinstance(img_size, (tuple, list)) else img_size
+    default = getattr(args, 'imagenet_default_mean_and_std', True)
+    mean = staging.IMAGENET_DEFAULT_MEAN if default else staging.IMAGENET_INCEPTION_MEAN
+    aa_params = dict(translate_const=int(img_size_min * 0.45), img_mean=tuple([min(255, round(255 * x)) for x in mean]))
+    interpolation = getattr(args, 'train_interpolation', 'bicubic')
+    if interpolation and interpolation != 'random':
+        # _pil_interp (utils/transforms.py): every name but bicubic / lanczos / hamming means bilinear
+        aa_params['interpolation'] = interpolation if interpolation in ('bicubic', 'lanczos', 'hamming') else 'bilinear'
+    return M.RandAugment(aa, aa_params)
+
+
+def cls_staged_loader(data_loader, args, device=None, train=True, erase_float32=True, rand_augment=None):
     """Wraps a classification DataLoader in ``multimae_amd.ClsStagedLoader``: it yields ``(samples, targets)`` on the device, every
     batch copied on the stager's stream one step ahead.  With a transform that ends in the reference's prefetch form (``ToNumpy()``:
     uint8 (3, H, W)) the batch is copied as bytes and normalised -- and, for the training loader, erased per
@@ -341,13 +362,16 @@ def cls_staged_loader(data_loader, args, device=None, train=True, erase_float32=
     UNCHANGED ``build_transform`` passes ``re_prob=args.reprob`` and so already ends in ``RandomErasing(device='cpu')``
     (utils/datasets.py:177, utils/transforms_factory.py:127-129): with it pass ``erase_float32=False``, which only moves the copy
     off the compute stream, or every sample is erased twice.  The loop's ``.to(device, non_blocking=True)``
-    (run_finetuning_cls.py:510-511, :593-594) becomes a no-op."""
+    (run_finetuning_cls.py:510-511, :593-594) becomes a no-op.
+    ``rand_augment``: the policy of ``rand_augment(args)``; the training loader's uint8 batches are then augmented on the device
+    before they are normalised, and the host transform must be built with ``auto_augment=None, color_jitter=None``."""
     from multimae_amd import staging
     default = getattr(args, 'imagenet_default_mean_and_std', True)
     mean = staging.IMAGENET_DEFAULT_MEAN if default else staging.IMAGENET_INCEPTION_MEAN
     std = staging.IMAGENET_DEFAULT_STD if default else staging.IMAGENET_INCEPTION_STD
     device = torch.device(device if device is not None else getattr(args, 'device', 'cuda'))
-    stager = staging.ClsStager(device, mean, std, random_erasing=random_erasing(args) if train else None, erase_float32=erase_float32)
+    stager = staging.ClsStager(device, mean, std, random_erasing=random_erasing(args) if train else None, erase_float32=erase_float32,
+                               rand_augment=rand_augment if train else None)
     return staging.ClsStagedLoader(data_loader, stager)
 
 

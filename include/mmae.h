@@ -1057,6 +1057,43 @@ int mmae_random_erase(float* x, const int32_t* table, int B, int C, int H, int W
 int mmae_ingest_rgb_u8_chw_erase(const uint8_t* x, const float* lut, const int32_t* table, float* y,
                                  int B, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * RandAugment (csrc/randaug.hip; multimae_amd/rand_augment.py, staging.ClsStager): RandAugment.__call__ / AugmentOp.__call__
+ * (utils/auto_augment.py:341-356, 624-636), the per-image step of the classification training transform between crop / flip and
+ * the tensor conversion (utils/transforms_factory.py:85-99), on the device.  Every random choice of the reference is made on the
+ * host, in its order, and the level functions are evaluated there; the table carries their results.
+ *   table   int32 [B][MMAE_RA_ROW] on the device, row b for sample b:
+ *           word 0      n, the number of layers, in [0, MMAE_RA_MAX_LAYERS] (clamped to it)
+ *           words 1-3   the fill colour R, G, B of the geometric ops (the low 8 bits count)
+ *           layer l at words 4 + 16 l:
+ *             +0        op: 0 none, 1 AutoContrast, 2 Equalize, 3 Invert, 4 Posterize, 5 Solarize, 6 SolarizeAdd, 7 Color,
+ *                       8 Contrast, 9 Brightness, 10 Sharpness, 11 Affine (Rotate, ShearX/Y, TranslateX/YRel); any other
+ *                       value is a no-op
+ *             +1        Affine: PIL's resampling code, 2 bilinear or 3 bicubic (anything else makes the layer a no-op)
+ *             +2        integer argument: Posterize bits to keep (0-8), Solarize threshold, SolarizeAdd addend
+ *             +3        Color / Contrast / Brightness / Sharpness: the bits of the f32 enhancement factor
+ *             +4..+15   Affine: the six f64 coefficients (a, b, c, d, e, f) of Image.transform(AFFINE), low word first
+ *   layers  apply in order, each to the previous layer's output; AutoContrast, Equalize and Contrast take their statistics
+ *           (per-channel extrema / histogram, the grey image's mean) from that output.  Per op the bytes are PIL's:
+ *           Affine      source (a (x + .5) + b (y + .5) + c, d (x + .5) + e (y + .5) + f) in f64; outside [0, W) x [0, H) the
+ *                       fill colour; else minus .5, 4 x 4 taps clamped to the image through the a = -1 cubic in Horner form
+ *                       (2 x 2 through two lerps for bilinear), clipped to [0, 255] and truncated
+ *           enhancers   Image.blend(degenerate, image, f): d + f (s - d) in f32, truncated, clipped first when f is outside
+ *                       [0, 1]; degenerate: Brightness 0, Color the grey value (19595 R + 38470 G + 7471 B + 0x8000) >> 16,
+ *                       Contrast int(mean(grey) + .5), Sharpness the 3 x 3 SMOOTH filter (1 1 1 / 1 5 1 / 1 1 1) / 13 with
+ *                       the border copied
+ *           point ops   ImageOps.autocontrast / equalize / posterize / solarize / invert, SolarizeAdd below 128
+ * mmae_rand_augment_u8: x uint8 [B][3][H][W] -> y uint8 of the same shape, not overlapping x.  `layers` in
+ * [1, MMAE_RA_MAX_LAYERS] is the number of layer passes run: every sample's layers beyond it are dropped, so pass the policy's n
+ * (or the maximum).  scratch: 16-byte aligned device memory of at least mmae_rand_augment_scratch_bytes(B, H, W, layers) bytes
+ * (-1 for arguments out of range).  Every byte of y is written exactly once; nothing outside y and scratch is written.
+ * ------------------------------------------------------------------------- */
+#define MMAE_RA_MAX_LAYERS 4
+#define MMAE_RA_ROW 68               /* int32 words per table row: 4 + 16 * MMAE_RA_MAX_LAYERS */
+int64_t mmae_rand_augment_scratch_bytes(int B, int H, int W, int layers);
+int mmae_rand_augment_u8(const uint8_t* x, const int32_t* table, uint8_t* y, void* scratch, int64_t scratch_bytes,
+                         int B, int H, int W, int layers, void* stream);
+
 /* hardware probes used by tests/ to pin instruction semantics the kernels rely on */
 /* SemSegInputAdapter(interpolate_class_emb=True) (input_adapters.py:192-198): the class-embedding image resized by 1 / patch with
  * nn.Upsample(bilinear) -- per token the mean of the centre taps -- as out f32 [B][E][H/ph][W/pw] (then projected like a 1 x 1 patch

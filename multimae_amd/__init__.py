@@ -12,6 +12,7 @@ from .criterion import (LabelSmoothingCrossEntropy, MaskedCrossEntropyLoss, Mask
 from .ema import ModelEma  # noqa: F401
 from .mixup import Mixup  # noqa: F401
 from .random_erasing import RandomErasing  # noqa: F401
+from .rand_augment import RandAugment  # noqa: F401
 from .metrics import ClsMetric, DepthMetric, SegMetric, cls_accuracy, depth_metrics, seg_argmax  # noqa: F401
 from .input_adapters import PatchedInputAdapter, SemSegInputAdapter  # noqa: F401
 from .multimae import (MultiMAE, MultiViT, multivit_base, multivit_large,  # noqa: F401

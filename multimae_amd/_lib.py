@@ -24,6 +24,7 @@ MXFP8 = 4
 F16 = 5            # fp16 storage (the fp32 output adapters' 'h16' mode), see mmae.h
 U16, I32 = 6, 7    # mmae_ingest_depth only: host-decoded depth maps
 ERASE_MAX_RECTS, ERASE_ROW = 8, 68    # MMAE_ERASE_MAX_RECTS, MMAE_ERASE_ROW: the table of mmae_random_erase / mmae_ingest_rgb_u8_chw_erase
+RA_MAX_LAYERS, RA_ROW = 4, 68         # MMAE_RA_MAX_LAYERS, MMAE_RA_ROW: the table of mmae_rand_augment_u8
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_G, EPI_MUL = 0, 1, 2, 3, 4
 EPI_GELU_Y = 5     # bias + GELU with one output stream: aux ignored (a forward that no backward follows)
 

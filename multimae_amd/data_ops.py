@@ -130,6 +130,39 @@ def ingest_rgb_u8_chw(x: torch.Tensor, lut: torch.Tensor, table: torch.Tensor = 
     return out
 
 
+# -------------------------------------------------------------------------------------- RandAugment (csrc/randaug.hip) --
+# The table is RandAugment.draw()'s (multimae_amd/rand_augment.py; layout in include/mmae.h, "RandAugment").
+
+RA_ROW_WORDS, RA_MAX_LAYERS = _lib.RA_ROW, _lib.RA_MAX_LAYERS
+
+
+def rand_augment_u8(x: torch.Tensor, table: torch.Tensor, out: torch.Tensor = None, layers: int = RA_MAX_LAYERS) -> torch.Tensor:
+    """Applies the layers of ``table`` (int32 (B, 68) on the device) to the contiguous uint8 (B, 3, H, W) batch ``x``; returns a new
+    tensor (or ``out``, which must not be ``x``: the geometric ops read neighbours).  ``layers``: the layer passes to run, the
+    policy's ``n`` -- a sample's layers beyond it are dropped; the default runs every layer a row can hold."""
+    ops._require_gpu(x, 'x')
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f'rand_augment_u8: expected a contiguous non-empty (B, 3, H, W) uint8 batch, got {tuple(x.shape)} {x.dtype}')
+    B, _, H, W = x.shape
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or tuple(table.shape) != (B, RA_ROW_WORDS) \
+            or not table.is_contiguous() or table.device != x.device:
+        got = f'{tuple(table.shape)} {table.dtype} on {table.device}' if torch.is_tensor(table) else type(table).__name__
+        raise ValueError(f'rand_augment_u8: table must be a contiguous int32 ({B}, {RA_ROW_WORDS}) tensor on {x.device}, got {got}')
+    if isinstance(layers, bool) or not isinstance(layers, int) or not 1 <= layers <= RA_MAX_LAYERS:
+        raise ValueError(f'rand_augment_u8: layers must be an int in [1, {RA_MAX_LAYERS}], got {layers!r}')
+    out = _out(out, (B, 3, H, W), torch.uint8, x.device, 'rand_augment_u8')
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError('rand_augment_u8: out must not be x')
+    lib = _lib.load()
+    nbytes = lib.mmae_rand_augment_scratch_bytes(B, H, W, layers)
+    if nbytes < 0:
+        raise ValueError(f'rand_augment_u8: no scratch size for shape {tuple(x.shape)}, layers {layers}')
+    scratch = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.mmae_rand_augment_u8(x.data_ptr(), table.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel(), B, H, W,
+                                        layers, ops._stream()), 'rand_augment_u8')
+    return out
+
+
 def depth_standardize_(x: torch.Tensor, lo: float = 0.1, hi: float = 0.9, eps: float = 1e-6) -> torch.Tensor:
     """``truncated_depth_standardize`` in place, on a contiguous f32 (B, ...) map (the kernel allows y to alias x)."""
     ops._require_gpu(x, 'depth')

@@ -17,7 +17,8 @@ Depth comes out as (B, 1, H, W) f32, standardised on the copy stream when ``stan
 launch for the compact form); the training loop must then not standardise it again.
 
 ``ClsStager`` / ``ClsStagedLoader`` (end of the file) do the same for the ``(images, target)`` batches of classification
-fine-tuning: uint8 (B, 3, H, W) images normalised and randomly erased by one launch on the copy stream (csrc/erase.hip).
+fine-tuning: uint8 (B, 3, H, W) images normalised and randomly erased by one launch on the copy stream (csrc/erase.hip), after
+RandAugment on the bytes when a policy is given (csrc/randaug.hip).
 """
 from __future__ import annotations
 
@@ -313,12 +314,20 @@ class ClsStager(BatchStager):
     ``erase_float32``: a float32 batch comes from a host transform that has already normalised it.  If that transform also ends in
     the reference's ``RandomErasing(device='cpu')`` -- ``create_transform`` appends it whenever ``re_prob > 0``
     (utils/transforms_factory.py:127-129) -- erasing here would erase every sample a second time: pass ``erase_float32=False`` then,
-    and float32 batches are only copied (no table is drawn for them).  uint8 batches are erased either way."""
+    and float32 batches are only copied (no table is drawn for them).  uint8 batches are erased either way.
+    ``rand_augment``: a ``multimae_amd.RandAugment``; a uint8 batch is then augmented on the copy stream between the byte copy and the
+    normalise-and-erase launch (``mmae_rand_augment_u8``), where the reference's transform has RandAugment.  Its table is drawn at
+    stage time, before the erase table: the reference's order within a batch.  The host transform must then not augment
+    (``auto_augment=None, color_jitter=None``).  A float32 batch is already normalised and cannot be augmented: ``ValueError``."""
 
-    def __init__(self, device=None, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, random_erasing=None, erase_float32=True):
+    def __init__(self, device=None, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, random_erasing=None, erase_float32=True,
+                 rand_augment=None):
+        if rand_augment is not None and not (callable(getattr(rand_augment, 'draw', None)) and hasattr(rand_augment, 'num_layers')):
+            raise ValueError(f'ClsStager: rand_augment must be a multimae_amd.RandAugment, got {type(rand_augment).__name__}')
         super().__init__(device, mean, std)
         self.random_erasing = random_erasing
         self.erase_float32 = bool(erase_float32)
+        self.rand_augment = rand_augment
 
     def bytes_per_batch(self, batch) -> Dict[str, int]:
         images, target = self._pair(batch)
@@ -338,12 +347,20 @@ class ClsStager(BatchStager):
             raise ValueError(f'ClsStager: target: {got} is not a tensor of {images.shape[0]} rows')
         return images, target
 
+    def _accept(self, item):
+        """``_pair`` plus what this stager's settings rule out"""
+        images, target = self._pair(item)
+        if self.rand_augment is not None and cls_form(images) != 'compact':
+            raise ValueError('ClsStager: rand_augment is set and the images are float32: a normalised batch cannot be augmented '
+                             '(hand over the uint8 prefetch form)')
+        return images, target
+
     def stage(self, item, into=None, after: Optional[torch.cuda.Event] = None) -> StagedBatch:
         """Queue one ``(images, target)`` batch.  ``into``: a caller-owned ``(x, target)`` pair of static device tensors to write
         instead of new ones; the copy stream first waits on ``after`` (``BatchStager.stage``)."""
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError('ClsStager.stage: not allowed inside a graph capture (stage between replays, with into=)')
-        images, target = self._pair(item)
+        images, target = self._accept(item)
         batch = {'images': images, 'target': target}
         forms = {'images': cls_form(images), 'target': 'reference'}
         specs = {'images': (tuple(images.shape), torch.float32), 'target': (tuple(target.shape), target.dtype)}
@@ -359,7 +376,11 @@ class ClsStager(BatchStager):
         batch's event has completed."""
         if self.random_erasing is None:
             return None
-        host = torch.from_numpy(self.random_erasing.draw(tuple(shape))).pin_memory()
+        return self._upload(self.random_erasing.draw(tuple(shape)), hold)
+
+    def _upload(self, table, hold):
+        """a table drawn on the host -> the device, from a pinned copy held until the batch's event has completed"""
+        host = torch.from_numpy(table).pin_memory()
         hold.append(host)
         return host.to(self.device, non_blocking=True)
 
@@ -372,6 +393,9 @@ class ClsStager(BatchStager):
             return d
         d = torch.empty(h.shape, dtype=h.dtype, device=self.device)
         d.copy_(h, non_blocking=True)
+        if self.rand_augment is not None and self.rand_augment.num_layers > 0:   # its table first, then the erase table
+            d = data_ops.rand_augment_u8(d, self._upload(self.rand_augment.draw(tuple(h.shape)), hold),
+                                         layers=self.rand_augment.num_layers)
         return data_ops.ingest_rgb_u8_chw(d, self.table, self._table(h.shape, hold), out=o)
 
     def get(self, staged: StagedBatch):
