@@ -1191,6 +1191,33 @@ int mmae_upsample2x_fwd(const float* x, float* y, int B, int h, int w, int C, vo
 int mmae_upsample2x_bwd(const float* g, float* dx, int B, int h, int w, int C, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Implicit-GEMM form of the same stride-1 convolutions, csrc/conv3x3_igemm.hip: the bf16 MFMA fed from an LDS halo image of the
+ * input tile, staged once and used by all nine taps; nothing 9 C wide exists in HBM.  Serves the stride-1 nn.Conv2d(kernel_size=3,
+ * padding=1) of ResidualConvUnit_custom (output_adapter_utils.py:74-92,110-123), scratch.layer_rn (output_adapter_utils.py:138-173)
+ * and the DPT regression head (output_adapters.py:628,630) where the geometry is eligible; selected by
+ * engine.set_conv3x3_impl('implicit'), the gather path above otherwise.  Maps channels-last f32, weights bf16.  No float atomics;
+ * a fixed summation order, results bit-equal from run to run; one launch over the whole batch.
+ * Eligibility (anything else: MMAE_EINVAL, nothing launched): Cin % 32 == 0, Cout % 32 == 0, every map and weight pointer 16-byte
+ * aligned, fewer than 2^40 elements per map (64-bit addresses: B = 64, 256 x 256, 128 channels is inside).
+ *   igemm_fwd:     y[b][oy][ox][o] = sum_(ky, kx, c) a(x[b][oy + ky - 1][ox + kx - 1][c]) wp[o][(3 ky + kx) Cin + c] + bias[o]
+ *                  + resid[b][oy][ox][o]; a(v) = the round-to-nearest-even bf16 of v, of max(v, 0) when relu != 0, and 0 outside the
+ *                  map -- the operands the gather path's GEMM sees; f32 accumulation.  x f32 [B][h][w][Cin] (not modified), wp bf16
+ *                  [Cout][9 Cin] as mmae_conv3x3_weight_pack writes it, bias f32 [Cout] or NULL, resid f32 [B][h][w][Cout] or NULL,
+ *                  y f32 [B][h][w][Cout] (not x).
+ *   igemm_dgrad:   dx[b][iy][ix][c] = m * sum_(ky, kx, o) bf16(dy[b][iy + 1 - ky][ix + 1 - kx][o]) wp[o][(3 ky + kx) Cin + c]
+ *                  + addend[b][iy][ix][c], m = (xmask[b][iy][ix][c] > 0) or 1 when xmask is NULL, addend NULL: 0 -- the semantics of
+ *                  mmae_gemm dY x W + mmae_conv3x3_col2im.  dy f32 [B][h][w][Cout], wpt the weight of weight_pack_t, dx f32
+ *                  [B][h][w][Cin] (not dy).  It is igemm_fwd run on dy against wpt, mask and addend in the epilogue.
+ *   weight_pack_t: wpt[c][(8 - t) Cout + o] = wp[o][t Cin + c], t = 3 ky + kx: the packed bf16 weight transposed and tap-reversed,
+ *                  [Cin][9 Cout]; element-wise, bit-exact.
+ * ------------------------------------------------------------------------- */
+int mmae_conv3x3_igemm_fwd(const float* x, const void* wp, const float* bias, const float* resid, float* y, int B, int h, int w, int Cin,
+                           int Cout, int relu, void* stream);
+int mmae_conv3x3_igemm_dgrad(const float* dy, const void* wpt, const float* xmask, const float* addend, float* dx, int B, int h, int w,
+                             int Cout, int Cin, void* stream);
+int mmae_conv3x3_weight_pack_t(const void* wp, void* wpt, int Cout, int Cin, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * The DPT head's regression tail and the weights of its transposed convolutions (DPTOutputAdapter, output_adapters.py:576-759),
  * csrc/dpt.hip.  No float atomics; results are bit-equal from run to run; no host synchronisation; f32 arithmetic in both
  * precision modes.

@@ -27,6 +27,7 @@ ALIGN = 64  # elements
 _state = {
     'act_dtype': torch.bfloat16,     # bf16 speed mode | float32 exact parity mode
     'direct_grads': False,           # backward accumulates straight into p.grad and returns None
+    'conv3x3_impl': 'gather',        # dense 3 x 3 convolutions: 'gather' (im2col + GEMM) | 'implicit' (implicit GEMM where eligible)
     'adapter_streams': False,
     'wgrad_stream': False,           # direct-grad mode: weight-gradient GEMMs / bias column sums on a side stream per compute stream        # run the independent output adapters on separate HIP streams
     'fp32_adapter_gemm': 'h16',      # fp32_output_adapters in bf16 speed mode: 'h16' (fp16 STORAGE: the bf16 pipeline's kernels with TF32's significand) | 'f16' (f32 tensors, fp16 operands) | 'x3' (split bf16) | 'exact'
@@ -294,6 +295,23 @@ def set_fp32_adapter_gemm(mode: str) -> None:
     'exact': f32-input MFMA (bit-level fmaf chain, 1/16 the bf16 rate)."""
     assert mode in ('h16', 'f16', 'x3', 'exact')
     _state['fp32_adapter_gemm'] = mode
+
+
+def conv3x3_impl() -> str:
+    return _state['conv3x3_impl']
+
+
+def set_conv3x3_impl(impl: str) -> None:
+    """How the dense 3 x 3 convolutions of the DPT stack (functions.conv3x3_fwd / conv3x3_bwd: Conv3x3, ResidualConvUnit_custom,
+    FeatureFusionBlock_custom, scratch.layer_rn, the DPT head) run:
+    'gather' (default): im2col into a [pixels, 9 C] buffer + the engine's GEMM; GEMM + col2im for the data gradient.
+    'implicit': where ops.conv3x3_igemm_ok holds (bf16 mode, stride 1, Cin and Cout multiples of 32, a 16-byte aligned map) the forward
+          is ONE implicit-GEMM launch over the whole batch and the data gradient one weight transpose plus one launch
+          (csrc/conv3x3_igemm.hip): no gathered rows, no chunks.  The weight gradient still gathers.  Any other convolution takes the
+          gather path unchanged, bit for bit, and silently."""
+    if impl not in ('gather', 'implicit'):
+        raise ValueError(f"set_conv3x3_impl: 'gather' or 'implicit', not {impl!r}")
+    _state['conv3x3_impl'] = impl
 
 
 def direct_grads() -> bool:

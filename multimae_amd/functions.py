@@ -1533,9 +1533,17 @@ def _col_buffer(like: Tensor, nbytes: int) -> Tensor:
     return torch.empty(((nbytes + 3) // 4,), device=like.device, dtype=torch.float32)
 
 
+def _conv_implicit(x: Tensor, Cin: int, Cout: int, stride: int, dtype, other: Optional[Tensor]) -> bool:
+    """engine.set_conv3x3_impl('implicit') and a convolution the implicit-GEMM kernel takes (ops.conv3x3_igemm_ok; `other`: the residual
+    or addend map of the call).  Anything else runs the gather path below, unchanged."""
+    return (engine.conv3x3_impl() == 'implicit' and ops.conv3x3_igemm_ok(x, Cin, Cout, stride, dtype)
+            and (other is None or (other.is_contiguous() and other.data_ptr() % 16 == 0)))
+
+
 def conv3x3_fwd(x: Tensor, wp: Tensor, bias: Optional[Tensor], stride: int, relu: bool, resid: Optional[Tensor], cap: int) -> Tensor:
     """y [B, ho, wo, Cout] f32 = conv3x3(relu?(x)) + bias + resid on the f32 NHWC map x: per chunk of samples one im2col gather and one
-    GEMM against the packed weight wp [Cout, 9 Cin] (bias and residual in the GEMM's epilogue)."""
+    GEMM against the packed weight wp [Cout, 9 Cin] (bias and residual in the GEMM's epilogue).  Under
+    engine.set_conv3x3_impl('implicit') an eligible convolution is ONE implicit-GEMM launch over the whole batch instead."""
     B, h, w, Cin = x.shape
     Cout, K9 = wp.shape
     ho, wo = ops.conv_out_size(h, stride), ops.conv_out_size(w, stride)
@@ -1544,6 +1552,8 @@ def conv3x3_fwd(x: Tensor, wp: Tensor, bias: Optional[Tensor], stride: int, relu
         raise ValueError(f'conv3x3_fwd: a {tuple(x.shape)} map does not fit the [{Cout}, {K9}] packed weight'
                          + ('' if resid is None else f' and the {tuple(resid.shape)} residual'))
     y = _new((B, ho, wo, Cout), x, torch.float32)
+    if _conv_implicit(x, Cin, Cout, stride, wp.dtype, resid):
+        return ops.conv3x3_igemm_fwd(x, wp, bias, resid, y, B, h, w, Cin, Cout, relu)     # one launch, no gathered rows; cap unused
     y2 = y.view(B * R1, Cout)
     r2 = resid.view(B * R1, Cout) if resid is not None else None
     esz = wp.element_size()
@@ -1562,7 +1572,8 @@ def conv3x3_bwd(dy: Tensor, x: Tensor, wp: Tensor, stride: int, relu: bool, adde
                 need_dw: bool):
     """Gradients of conv3x3_fwd for dy [B, ho, wo, Cout] f32: (dx [B, h, w, Cin] f32 = relu'(x) * conv^T(dy) + addend, dwp [Cout, 9 Cin]
     f32 in the packed order), None where not needed.  Per chunk: the gathered rows are recomputed (never saved) for dY^T x col,
-    then the same buffer takes dY x W, which col2im gathers into dx."""
+    then the same buffer takes dY x W, which col2im gathers into dx.  Under engine.set_conv3x3_impl('implicit') an eligible dx is one
+    weight transpose plus one implicit-GEMM launch; the weight gradient gathers either way."""
     B, h, w, Cin = x.shape
     Cout, K9 = wp.shape
     ho, wo = ops.conv_out_size(h, stride), ops.conv_out_size(w, stride)
@@ -1571,11 +1582,20 @@ def conv3x3_bwd(dy: Tensor, x: Tensor, wp: Tensor, stride: int, relu: bool, adde
         raise ValueError(f'conv3x3_bwd: a {tuple(dy.shape)} gradient and a {tuple(x.shape)} map do not fit the [{Cout}, {K9}] packed weight'
                          + ('' if addend is None else f' and the {tuple(addend.shape)} addend'))
     f32 = torch.float32
-    dya = ops.cast(dy.reshape(B * R1, Cout), wp.dtype)
-    dx = _new((B, h, w, Cin), x, f32) if need_dx else None
-    dwp = _new((Cout, K9), x, f32) if need_dw else None
     esz = 4 if need_dx else wp.element_size()
-    nb = _col_rows(B, R1, K9, esz, cap)
+    nb = _col_rows(B, R1, K9, esz, cap)                  # the chunks of the gather path, whichever way dx is computed: dwp keeps its bits
+    if need_dx and _conv_implicit(x, Cin, Cout, stride, wp.dtype, addend) and _conv_implicit(dy, Cout, Cin, stride, wp.dtype, None):
+        # the data gradient as ONE implicit-GEMM launch on dy against the transposed, tap-reversed weight; mask and addend in its epilogue
+        dx = _new((B, h, w, Cin), x, f32)
+        ops.conv3x3_igemm_dgrad(dy, ops.conv3x3_weight_pack_t(wp), x if relu else None, addend, dx, B, h, w, Cout, Cin)
+        if not need_dw:
+            return dx, None
+        need_dx, esz = False, wp.element_size()          # the weight gradient still gathers: bf16 rows only
+        dya = ops.cast(dy.reshape(B * R1, Cout), wp.dtype)
+    else:
+        dya = ops.cast(dy.reshape(B * R1, Cout), wp.dtype)
+        dx = _new((B, h, w, Cin), x, f32) if need_dx else None
+    dwp = _new((Cout, K9), x, f32) if need_dw else None
     ws = _col_buffer(x, nb * R1 * K9 * esz)
     for b0 in range(0, B, nb):
         n = min(nb, B - b0)

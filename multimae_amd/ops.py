@@ -1658,6 +1658,72 @@ def conv3x3_weight_unpack(dwp: Tensor, dw: Tensor, accumulate: bool) -> Tensor:
     return dw
 
 
+# the implicit-GEMM form of the stride-1 convolutions (csrc/conv3x3_igemm.hip)
+CONV3X3_IGEMM_TILE = (8, 32)      # == TH, TW of csrc/conv3x3_igemm.hip: output pixels (rows, columns) of one workgroup
+CONV3X3_IGEMM_CHANNELS = 32       # Cin and Cout are multiples of it (one K stage / one MFMA tile of output channels)
+
+
+def _al16(t: Optional[Tensor]) -> bool:
+    return t is None or t.data_ptr() % 16 == 0
+
+
+def conv3x3_igemm_ok(x: Tensor, Cin: int, Cout: int, stride: int, dtype: torch.dtype) -> bool:
+    """The eligibility rule of the implicit-GEMM convolution, in one place: bf16 operands, stride 1, Cin and Cout multiples of 32, and
+    a contiguous, 16-byte aligned f32 map x [B, h, w, Cin] of fewer than 2^40 elements (on either side of the convolution).  The
+    other maps of a call (output, residual, addend) come from the allocator; the wrappers below check them again."""
+    if dtype != torch.bfloat16 or stride != 1 or Cin <= 0 or Cout <= 0 or Cin % CONV3X3_IGEMM_CHANNELS or Cout % CONV3X3_IGEMM_CHANNELS:
+        return False
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[-1] != Cin or x.numel() == 0 or not x.is_contiguous() or not _al16(x):
+        return False
+    return (x.numel() // Cin) * max(Cin, Cout) < (1 << 40)
+
+
+def _igemm_check(what: str, B: int, h: int, w: int, Ck: int, Cn: int, src: Tensor, wgt: Tensor, dst: Tensor,
+                 per_ch: Optional[Tensor], extra: Sequence[Optional[Tensor]]) -> None:
+    """src f32 [B, h, w, Ck] x wgt bf16 [Cn, 9 Ck] -> dst f32 [B, h, w, Cn]; `extra`: optional f32 maps shaped like dst"""
+    pix = B * h * w
+    f32 = torch.float32
+    if (min(B, h, w, Ck, Cn) <= 0 or Ck % CONV3X3_IGEMM_CHANNELS or Cn % CONV3X3_IGEMM_CHANNELS or pix * max(Ck, Cn) >= (1 << 40)
+            or src.dtype != f32 or dst.dtype != f32 or wgt.dtype != torch.bfloat16 or src.numel() < pix * Ck or dst.numel() < pix * Cn
+            or wgt.numel() < 9 * Ck * Cn or any(t is not None and (t.dtype != f32 or t.numel() < pix * Cn) for t in extra)
+            or (per_ch is not None and (per_ch.dtype != f32 or per_ch.numel() < Cn))
+            or not all(t is None or t.is_contiguous() for t in (src, wgt, dst, per_ch, *extra))):
+        raise ValueError(f'{what}: {B} x {h} x {w} maps with {Ck} -> {Cn} channels (multiples of {CONV3X3_IGEMM_CHANNELS}) need contiguous '
+                         f'buffers of {pix * Ck} f32, {9 * Ck * Cn} bf16 and {pix * Cn} f32 elements; got {src.numel()} {src.dtype}, '
+                         f'{wgt.numel()} {wgt.dtype}, {dst.numel()} {dst.dtype} and {[None if t is None else t.numel() for t in extra]}')
+    if not all(_al16(t) for t in (src, wgt, dst, *extra)):
+        raise ValueError(f'{what}: every map and the weight must be 16-byte aligned')
+
+
+def conv3x3_igemm_fwd(x: Tensor, wp: Tensor, bias: Optional[Tensor], resid: Optional[Tensor], y: Tensor, B: int, h: int, w: int, Cin: int,
+                      Cout: int, relu: bool) -> Tensor:
+    """y f32 [B, h, w, Cout] = conv3x3(bf16(relu?(x))) + bias + resid for x f32 [B, h, w, Cin] and the packed bf16 weight wp [Cout, 9 Cin]:
+    one launch, the window taken from LDS (no gathered rows)"""
+    _igemm_check('conv3x3_igemm_fwd', B, h, w, Cin, Cout, x, wp, y, bias, (resid,))
+    check(_lib.load().mmae_conv3x3_igemm_fwd(x.data_ptr(), wp.data_ptr(), _p(bias), _p(resid), y.data_ptr(), B, h, w, Cin, Cout, int(relu), _stream()),
+          'conv3x3_igemm_fwd')
+    return y
+
+
+def conv3x3_igemm_dgrad(dy: Tensor, wpt: Tensor, xmask: Optional[Tensor], addend: Optional[Tensor], dx: Tensor, B: int, h: int, w: int,
+                        Cout: int, Cin: int) -> Tensor:
+    """dx f32 [B, h, w, Cin] = (xmask > 0) * conv3x3^T(bf16(dy)) + addend for dy f32 [B, h, w, Cout] and wpt = conv3x3_weight_pack_t(wp)"""
+    _igemm_check('conv3x3_igemm_dgrad', B, h, w, Cout, Cin, dy, wpt, dx, None, (xmask, addend))
+    check(_lib.load().mmae_conv3x3_igemm_dgrad(dy.data_ptr(), wpt.data_ptr(), _p(xmask), _p(addend), dx.data_ptr(), B, h, w, Cout, Cin, _stream()),
+          'conv3x3_igemm_dgrad')
+    return dx
+
+
+def conv3x3_weight_pack_t(wp: Tensor) -> Tensor:
+    """the packed bf16 weight [Cout, 9 Cin] -> [Cin, 9 Cout], transposed and tap-reversed: wpt[c][(8 - t) Cout + o] = wp[o][t Cin + c]"""
+    if wp.dim() != 2 or wp.dtype != torch.bfloat16 or wp.shape[1] % 9 or wp.numel() == 0 or not wp.is_contiguous():
+        raise ValueError(f'conv3x3_weight_pack_t: takes a contiguous bf16 [Cout, 9 Cin] packed weight; got {tuple(wp.shape)} {wp.dtype}')
+    Cout, Cin = wp.shape[0], wp.shape[1] // 9
+    wpt = torch.empty((Cin, 9 * Cout), device=wp.device, dtype=wp.dtype)
+    check(_lib.load().mmae_conv3x3_weight_pack_t(wp.data_ptr(), wpt.data_ptr(), Cout, Cin, _stream()), 'conv3x3_weight_pack_t')
+    return wpt
+
+
 def upsample2x_fwd(x: Tensor, B: int, h: int, w: int, C: int) -> Tensor:
     """F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) on the f32 NHWC map"""
     y = torch.empty((B, 2 * h, 2 * w, C), device=x.device, dtype=torch.float32)
